@@ -13,7 +13,13 @@ already resident in HBM.  With N > 1 GPUs every rank renders its own batch (rays
 and the per-ray outputs (rgb, accumulation, depth, semantics: 24 B/ray) are all-gathered over RCCL inside the
 timed step -- the only exchange the sharded path has.
 
-Prints ONE JSON line (rank 0).  `value` = field samples per second over all GPUs.
+Prints ONE JSON line (rank 0).  `value` = field samples per second over all GPUs; `ms_per_step` = one timed step.
+
+A plain run does only what that line needs: set-up, the warm-ups, the timed steps, the line.  `--full` adds everything
+else, after the timed steps: the live roofline launches, the secondary workloads (other matrix modes, proposal mode,
+training), the other subsystems, the CPU baseline, the N > 1 gather check and the full record in bench_secondary.json.
+`--dump-outputs DIR` writes the outputs of the last timed step as DIR/<name>.npy (float32; the inputs are seeded, so
+two builds run with the same arguments can be compared output for output).
 """
 
 from __future__ import annotations
@@ -111,18 +117,26 @@ def parse_args():
                     help="profiling aid (rocprofv3 -- python3 bench.py --variant ... --no-secondary --no-cpu-baseline): the "
                          "timed loop renders the M-uniform workload through another table / matrix mode; the JSON line "
                          "then names the variant and is NOT the headline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beside the headline: live roofline, secondary "
+                         "workloads, subsystems, CPU baseline, N > 1 gather check; full record in bench_secondary.json")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--no-image-hint", action="store_true",
                     help="do not tell the renderer that a batch is a pixel run of an 800-wide image (A/B of the XCD stripe mapping)")
-    ap.add_argument("--no-train", action="store_true", help="skip the secondary training-step timing")
+    ap.add_argument("--no-train", action="store_true", help="(--full) skip the secondary training-step timing")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="headline workload only (use under rocprofv3 so per-kernel averages are not mixed with the "
-                         "proposal-mode and training launches)")
+                    help="(--full) skip the secondary workloads and subsystems (use under rocprofv3 so per-kernel averages "
+                         "are not mixed with the proposal-mode and training launches)")
     ap.add_argument("--no-subsystems", action="store_true",
-                    help="skip the exporter / projection lines (10 M-point export, dense export, projection job)")
+                    help="(--full) skip the exporter / projection lines (10 M-point export, dense export, projection job)")
     ap.add_argument("--cpu-baseline-chunks", type=int, default=10,
-                    help="timed chunks of the CPU baseline (after 3 warm-ups; the median chunk time is reported)")
-    return ap.parse_args()
+                    help="(--full) timed chunks of the CPU baseline (after 3 warm-ups; the median chunk time is reported)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def setup_dist(n_gpus: int):
@@ -274,17 +288,19 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(args.warmup + i)
+        out = step(args.warmup + i)
     barrier()
     elapsed = time.perf_counter() - t0
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if dist.get_backend() == "gloo" else device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, last["buf"] if world > 1 else None)
 
     # ---- N > 1: the gathered buffer of the last step holds every rank's rows, in rank order (outside the timed region) ---
     gather_check = None
-    if world > 1:
+    if world > 1 and args.full:
         mine = last["packed"].double().sum(dim=0).cpu()  # [6] column sums of this rank's per-ray outputs
         sums = [None] * world
         dist.all_gather_object(sums, mine)
@@ -298,7 +314,7 @@ def main():
     # ---- roofline of the dominant kernel, measured live with HIP events on the launch stream -------------------------------
     roofline = None
     extra = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         avg = launch_time(lambda i: ops.render_rays(fh, scene_u, opts_for(batches[i % DISTINCT_BATCHES][5]),
                                                     *batches[i % DISTINCT_BATCHES][:4]), min(args.steps, 20))
         alg_bytes = R * (S * BYTES_PER_SAMPLE + BYTES_PER_RAY_IO)
@@ -338,7 +354,7 @@ def main():
         extra["uniform_samples_per_sec_single_launch"] = R * S / avg
 
     # ---- secondary numbers (rank 0, N=1): proposal-mode render and training iterations --------------------------------
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if rank == 0 and world == 1 and args.full and not args.no_secondary:
         extra.update(secondary_timings(args, cfg, params, fspec, batches, ops, fh, dh, scene_c, opts))
         if not args.no_subsystems:
             extra.update(subsystem_timings(args, params, device))
@@ -348,7 +364,7 @@ def main():
     # include the host's enqueue gaps (measured: the fp16-mode line read 1.47 ms after the baseline and 1.39-1.42 ms without it)
     cpu_baseline = None
     psnr = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu_baseline, psnr = run_cpu_baseline(args, params, fspec, pspecs, batches, ops, fh, scene_u, opts)
 
     if rank == 0:
@@ -380,7 +396,7 @@ def main():
         }
         if gather_check is not None:
             line["gather_check"] = gather_check
-        emit(line, extra)
+        emit(line, extra, full_record=args.full)
     if world > 1:
         dist.destroy_process_group()
 
@@ -468,18 +484,19 @@ def compact_line(line: dict, extra: dict) -> dict:
     return out
 
 
-def emit(line: dict, extra: dict):
-    """Full record -> bench_secondary.json (next to this file); the compact line -> stdout, LAST, under 4 KB."""
-    full = dict(line)
-    full.update(extra)
-    text = json.dumps(full)
-    try:
-        with open(os.path.join(ROOT, "bench_secondary.json"), "w") as fh_:
-            fh_.write(text + "\n")
-    except OSError as e:
-        print(f"bench.py: could not write bench_secondary.json: {e}", file=sys.stderr)
-    # stderr stays short too: the driver's captured tail holds stdout THEN stderr, cut to its last few KB
-    print(f"bench.py: full record ({len(text)} B) written to bench_secondary.json", file=sys.stderr, flush=True)
+def emit(line: dict, extra: dict, full_record: bool = True):
+    """Full record -> bench_secondary.json (next to this file; --full only); the compact line -> stdout, LAST, under 4 KB."""
+    if full_record:
+        full = dict(line)
+        full.update(extra)
+        text = json.dumps(full)
+        try:
+            with open(os.path.join(ROOT, "bench_secondary.json"), "w") as fh_:
+                fh_.write(text + "\n")
+        except OSError as e:
+            print(f"bench.py: could not write bench_secondary.json: {e}", file=sys.stderr)
+        # stderr stays short too: the driver's captured tail holds stdout THEN stderr, cut to its last few KB
+        print(f"bench.py: full record ({len(text)} B) written to bench_secondary.json", file=sys.stderr, flush=True)
     short = json.dumps(compact_line(line, extra))
     if len(short) >= MAX_LINE_BYTES:  # never let the driver's line grow past what it reads: drop the secondaries first
         c = compact_line(line, extra)
@@ -487,6 +504,25 @@ def emit(line: dict, extra: dict):
         short = json.dumps(c)
     assert len(short) < MAX_LINE_BYTES, len(short)
     print(short, flush=True)
+
+
+MAX_DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, out: dict, gathered=None):
+    """The last timed step's outputs as ``path/<name>.npy``, float32: the per-ray tensors cn_render_rays hands its caller
+    (rgb, accumulation, depth, semantics, semantics_colormap: 2.4 MB for 65 536 rays) and, with N > 1 GPUs, the
+    all-gathered [N x rays, 6] buffer -- every row up to 64 MB in all, beyond that an evenly strided subset of its rows."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in out.items()}
+    if gathered is not None:
+        g = gathered.detach().float().cpu()
+        room = max(1, (MAX_DUMP_BYTES - sum(a.nbytes for a in arrays.values())) // (g.shape[1] * 4))
+        arrays["gathered"] = g[::-(-g.shape[0] // room)].numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def tcnn_f16_field(params, device):

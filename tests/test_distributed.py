@@ -283,7 +283,7 @@ def test_bench_two_ranks_rehearsal():
     """``bench.py --gpus 2`` launched exactly as the driver launches it (``torch.distributed.run``, fresh child processes),
     rehearsed on this box's single GPU (``BENCH_REHEARSE_ON_ONE_GPU=1``: both ranks on cuda:0, exchange over gloo; on a
     multi-GPU node the same code path runs one rank per GPU over RCCL): one JSON line from rank 0, n_gpus 2, the sharding
-    string, weak scaling (twice the work per step), and the gathered buffer holds both ranks' rows."""
+    string, weak scaling (twice the work per step), and (--full) the gathered buffer holds both ranks' rows."""
     import json
     import os
     import socket
@@ -296,7 +296,7 @@ def test_bench_two_ranks_rehearsal():
         port = s.getsockname()[1]
     env = dict(os.environ, BENCH_REHEARSE_ON_ONE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"]
+           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -324,7 +324,7 @@ def test_bench_plain_invocation_launches_its_own_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(BENCH_REHEARSE_ON_ONE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

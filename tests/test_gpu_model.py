@@ -503,10 +503,10 @@ def test_named_background_colours(scene):
 
 
 def test_bench_line_contract():
-    """bench.py as the driver runs it (DEFAULT flags: every secondary workload, the CPU baseline; fewer steps only) prints ONE
-    stdout line, under 4 KB, that round-trips through json with the driver's keys plus ``roofline`` and ``cpu_baseline``; the full
-    record goes to bench_secondary.json.  (Round 4's line had grown to 20.6 KB and the driver could not read it -- this test ran
-    with --no-secondary and never saw the line the driver gets.)"""
+    """bench.py --full (every secondary workload, the CPU baseline; fewer steps only) prints ONE stdout line, under 4 KB, that
+    round-trips through json with the driver's keys plus ``roofline`` and ``cpu_baseline``; the full record goes to
+    bench_secondary.json.  (Round 4's line had grown to 20.6 KB and the driver could not read it -- this test ran with
+    --no-secondary and never saw the line the driver gets.)"""
     import subprocess
     import sys
 
@@ -516,7 +516,7 @@ def test_bench_line_contract():
         os.remove(side)
     # (10 steps after 5 warm-ups: with 3 + 1 the whole timed region is 8 ms and fell inside the clock ramp of an idle device
     #  once -- 16 ms per step on a fresh box)
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "10", "--warmup", "5"],
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "10", "--warmup", "5", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=root)
     assert p.returncode == 0, p.stderr[-2000:]
     assert len(p.stderr) < 4096, len(p.stderr)  # the driver's captured tail is stdout THEN stderr: keep both short
@@ -552,6 +552,43 @@ def test_bench_line_contract():
     m = full["roofline_mfma"]
     assert m["bound"] == "mfma" and m["unit"] == "TFLOP/s" and abs(m["frac"] - m["achieved"] / m["peak"]) < 1e-3
     assert "roofline" in full["train_iteration"]["4096"] and "roofline" in full["export_pointcloud_c4"]
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain bench.py run (no --full) is the headline alone: the same contract keys, no roofline launches, secondaries or CPU
+    baseline, no bench_secondary.json.  ``--dump-outputs`` writes the last timed step's per-ray outputs as float32 .npy files,
+    and two runs with the same arguments write identical arrays (seeded inputs; one wave owns one ray)."""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    side = os.path.join(root, "bench_secondary.json")
+    if os.path.exists(side):
+        os.remove(side)
+    dumps = []
+    for k in range(2):
+        dump = tmp_path / f"run{k}"
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                            "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600, cwd=root)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 7 and d["warmup"] == 2 and d["n_gpus"] == 1
+        assert d["metric"] == "ray_samples_per_sec" and d["unit"] == "samples/s" and d["higher_is_better"] is True
+        assert d["dtype"].startswith("f32") and "bf16 hi+lo" in d["dtype"]
+        assert d["value"] > 1e9 and abs(d["ms_per_step"] * 1e-3 * d["value"] - 65536 * 192) / (65536 * 192) < 1e-6
+        assert d["roofline"] is None and d["cpu_baseline"] is None and "secondary" not in d
+        assert not os.path.exists(side)
+        arrays = {f.stem: np.load(f) for f in dump.glob("*.npy")}
+        assert set(arrays) == {"rgb", "accumulation", "depth", "semantics", "semantics_colormap"}
+        for name, a in arrays.items():
+            assert a.dtype == np.float32 and a.shape == (65536, 3 if name in ("rgb", "semantics_colormap") else 1), name
+            assert np.isfinite(a).all(), name
+        assert arrays["accumulation"].max() > 0.0
+        dumps.append(arrays)
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
 
 
 def test_pointcloud_export_at_c4_size():

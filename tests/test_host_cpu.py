@@ -217,3 +217,28 @@ def test_bench_compact_line_fits_the_driver():
     assert c["roofline"]["traffic"] == full["roofline"]["traffic"] and c["cpu_baseline"]["cores"] == 16
     assert all(isinstance(v, (int, float)) for v in c["secondary"].values())
     assert c["secondary"]["train_65536_ms"] == 15.56 and c["secondary"]["c4_seconds"] == 12.77
+
+
+def test_bench_dump_outputs_files_and_size_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float32 .npy per output tensor, values unchanged; the N > 1 all-gathered buffer is written
+    whole while it fits in the 64 MB budget and as an evenly strided subset of its rows beyond it."""
+    import importlib.util
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("_bench_for_test", os.path.join(root, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    g = torch.Generator().manual_seed(0)
+    out = {"rgb": torch.rand(64, 3, generator=g), "accumulation": torch.rand(64, 1, generator=g)}
+    gathered = torch.rand(4 * 64, 6, generator=g)
+    b.dump_outputs(str(tmp_path / "a"), out, gathered)
+    got = {f.stem: np.load(f) for f in (tmp_path / "a").glob("*.npy")}
+    assert set(got) == {"rgb", "accumulation", "gathered"}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["rgb"], out["rgb"].numpy()) and np.array_equal(got["gathered"], gathered.numpy())
+    # room for 1/3 of the gathered rows next to the per-ray outputs: every third row is kept
+    monkeypatch.setattr(b, "MAX_DUMP_BYTES", 64 * 4 * 4 + 86 * 6 * 4)
+    b.dump_outputs(str(tmp_path / "b"), out, gathered)
+    capped = np.load(tmp_path / "b" / "gathered.npy")
+    assert np.array_equal(capped, gathered.numpy()[::3])
+    assert capped.nbytes + 64 * 4 * 4 <= b.MAX_DUMP_BYTES
