@@ -80,6 +80,8 @@ class RenderOpts(C.Structure):
 
 
 MATRIX_FP32, MATRIX_SPLIT_BF16, MATRIX_F16 = 0, 1, 2  # cn_render_opts.matrix_precision
+# flags of the *_ex training entry points (CN_TRAIN_*): pass_semantic_gradients / use_gradient_scaling
+TRAIN_PASS_SEMANTIC_GRADIENTS, TRAIN_GRADIENT_SCALING = 1, 2
 
 
 class ProjectionJob(C.Structure):
@@ -162,17 +164,24 @@ SIGNATURES = {
     "cn_embedding_mean": (C.c_int, [_P, _I32, _I32, _P, _P]),
     "cn_train_render_backward": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _F, _P, _P, _P, _P, _P, _P, _P, _P,
                                            _P, _P]),
+    "cn_train_render_backward_ex": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _F, _P, _P, _P, _P, _P, _P, _P, _P,
+                                              _P, C.c_uint32, _P]),
     "cn_interlevel_backward": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _F, _P, _P, _P]),
     "cn_interlevel_backward_levels": (C.c_int, [_P, _P, C.POINTER(InterlevelLevel), _I32, _I64, _I32, _F, _P, _P]),
     "cn_field_backward": (C.c_int, [C.POINTER(FieldParams), C.POINTER(FieldParams), C.POINTER(Scene), _I32, _I32, _P,
                                     _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P, _P, _P]),
     "cn_field_backward_mp": (C.c_int, [C.POINTER(FieldParams), C.POINTER(FieldParams), C.POINTER(Scene), _I32, _I32, _P,
                                        _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P, _P, _I32, _P]),
+    "cn_field_backward_ex": (C.c_int, [C.POINTER(FieldParams), C.POINTER(FieldParams), C.POINTER(Scene), _I32, _I32, _P,
+                                       _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P, _P, _I32, C.c_uint32, _P]),
     "cn_proposal_backward": (C.c_int, [C.POINTER(DensityParams), C.POINTER(DensityParams), C.POINTER(Scene), _P, _P,
                                        _P, _P, _P, _I64, _I32, _P, _P]),
     "cn_field_backward_general_workspace_bytes": (C.c_size_t, [C.POINTER(FieldParams)]),
     "cn_field_backward_general": (C.c_int, [C.POINTER(FieldParams), C.POINTER(FieldParams), C.POINTER(Scene), _I32, _I32,
                                             _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P, _P, _P, C.c_size_t, _P]),
+    "cn_field_backward_general_ex": (C.c_int, [C.POINTER(FieldParams), C.POINTER(FieldParams), C.POINTER(Scene), _I32,
+                                               _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P, _P, C.c_uint32, _P,
+                                               C.c_size_t, _P]),
     "cn_ray_backward": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _P, _P]),
     "cn_pose_adjustment_backward": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _P, _P]),
     "cn_pose_regularizer": (C.c_int, [_P, _I32, _F, _F, _P, _P, _P]),

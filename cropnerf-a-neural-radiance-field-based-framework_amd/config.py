@@ -151,6 +151,8 @@ class FruitNerfModelConfig:
     use_average_appearance_embedding: bool = True
     interlevel_loss_mult: float = 1.0
     distortion_loss_mult: float = 0.002
+    # nerfstudio's scale_gradients_by_distance_squared on the field outputs (fruit_nerf.py:553-554); training gradients only
+    use_gradient_scaling: bool = False
     eval_num_rays_per_chunk: int = 1 << 15
     sh_input: str = "unit"
     # extension (not in the reference, which composites every sample): > 0 stops a ray in eval renders once its

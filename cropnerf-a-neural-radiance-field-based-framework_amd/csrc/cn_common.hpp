@@ -36,6 +36,9 @@ inline int check_launch(const char* what) {
 
 inline hipStream_t as_stream(cn_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
+// every CN_TRAIN_* bit the training entry points know (an unknown bit is refused, not ignored)
+constexpr unsigned TRAIN_FLAGS_ALL = CN_TRAIN_PASS_SEMANTIC_GRADIENTS | CN_TRAIN_GRADIENT_SCALING;
+
 // One-time, PER-DEVICE kernel setup (hipFuncSetAttribute(MaxDynamicSharedMemorySize), occupancy queries): a process that
 // uses several devices through the C ABI gets the attributes set on each of them, and a failed attribute call surfaces
 // as CN_ERR_LAUNCH with a message instead of a later opaque launch error.  init(device, value) returns a hipError_t.

@@ -1114,10 +1114,24 @@ extern "C" int cn_field_backward_mp(const cn_field_params* params, const cn_fiel
                                     const float* ends, const float* d_density, const float* d_rgb, const float* d_semantics,
                                     int64_t num_rays, int32_t num_samples, float* d_positions, float* d_directions,
                                     int32_t matrix_precision, cn_stream_t stream) {
+  return cn_field_backward_ex(params, grads, scene, app_mode, sh_unit_dir, app_mean, origins, directions, camera_indices, starts,
+                              ends, d_density, d_rgb, d_semantics, num_rays, num_samples, d_positions, d_directions,
+                              matrix_precision, 0u, stream);
+}
+
+extern "C" int cn_field_backward_ex(const cn_field_params* params, const cn_field_params* grads, const cn_scene* scene,
+                                    int32_t app_mode, int32_t sh_unit_dir, const float* app_mean, const float* origins,
+                                    const float* directions, const int64_t* camera_indices, const float* starts,
+                                    const float* ends, const float* d_density, const float* d_rgb, const float* d_semantics,
+                                    int64_t num_rays, int32_t num_samples, float* d_positions, float* d_directions,
+                                    int32_t matrix_precision, uint32_t flags, cn_stream_t stream) {
   CN_REQUIRE(params && grads && scene && origins && directions && starts && ends && d_density && d_rgb && d_semantics,
              CN_ERR_INVALID, "cn_field_backward: null argument");
   CN_REQUIRE(matrix_precision == CN_MATRIX_FP32 || matrix_precision == CN_MATRIX_SPLIT_BF16 || matrix_precision == CN_MATRIX_F16,
              CN_ERR_INVALID, "cn_field_backward: matrix_precision %d", matrix_precision);
+  CN_REQUIRE((flags & ~cn::TRAIN_FLAGS_ALL) == 0, CN_ERR_INVALID, "cn_field_backward: unknown flags 0x%x", (unsigned)flags);
+  // (CN_TRAIN_GRADIENT_SCALING needs nothing here: the render backward hands over scaled per-sample gradients)
+  const bool pass_sem = (flags & CN_TRAIN_PASS_SEMANTIC_GRADIENTS) != 0;
   CN_REQUIRE(app_mode != CN_APP_PER_CAMERA || camera_indices, CN_ERR_INVALID, "Camera indices are not provided.");
   CN_REQUIRE(app_mode != CN_APP_MEAN || app_mean, CN_ERR_INVALID, "cn_field_backward: app_mean required for CN_APP_MEAN");
   int rc = cn::validate_field(*params);
@@ -1175,6 +1189,9 @@ extern "C" int cn_field_backward_mp(const cn_field_params* params, const cn_fiel
   // kept as an independent device implementation for cross-checks
   const char* impl_env = getenv("CN_FIELD_BACKWARD_IMPL");  // read per call: one process can compare both
   const bool use_scalar = impl_env && std::strcmp(impl_env, "scalar") == 0;
+  CN_REQUIRE(!(use_scalar && pass_sem), CN_ERR_UNSUPPORTED,
+             "cn_field_backward: the scalar implementation (CN_FIELD_BACKWARD_IMPL=scalar) runs the semantic branch after the "
+             "base-MLP backward and does not implement CN_TRAIN_PASS_SEMANTIC_GRADIENTS");
   static cn::PerDevice<int> attrs;  // one-time kernel attributes, per device
   rc = attrs.get(
       [](int, int&) {
@@ -1182,11 +1199,14 @@ extern "C" int cn_field_backward_mp(const cn_field_params* params, const cn_fiel
                                            hipFuncAttributeMaxDynamicSharedMemorySize,
                                            (int)((size_t)cn::FIELD_ROWS * cn::LD * sizeof(float)));
         if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(cn::mf::field_backward_mfma_kernel<0>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)cn::mf::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(cn::mf::field_backward_mfma_kernel<1>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)cn::mf::LDS_BYTES);
+        for (const void* k : {reinterpret_cast<const void*>(cn::mf::field_backward_mfma_kernel<0>),
+                              reinterpret_cast<const void*>(cn::mf::field_backward_mfma_kernel<1>),
+                              reinterpret_cast<const void*>(cn::mf::field_backward_mfma_kernel<0, true>),
+                              reinterpret_cast<const void*>(cn::mf::field_backward_mfma_kernel<1, true>)}) {
+          e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cn::mf::LDS_BYTES);
+          if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
       },
       nullptr, "cn_field_backward");
   if (rc) return rc;
@@ -1205,12 +1225,22 @@ extern "C" int cn_field_backward_mp(const cn_field_params* params, const cn_fiel
       if (A.cells.num_levels > 0) A.coarse.base = nullptr;  // level 0 is cell-major then
     }
     // (split-bf16 keeps ~fp32 products in the forward; its gradient is the exact-fp32 kernel's)
-    if (matrix_precision == CN_MATRIX_F16)
-      hipLaunchKernelGGL(cn::mf::field_backward_mfma_kernel<1>, dim3(cn::grid_for(ntiles, 1, 256)), dim3(cn::mf::NT),
-                         cn::mf::LDS_BYTES, cn::as_stream(stream), A);
-    else
-      hipLaunchKernelGGL(cn::mf::field_backward_mfma_kernel<0>, dim3(cn::grid_for(ntiles, 1, 256)), dim3(cn::mf::NT),
-                         cn::mf::LDS_BYTES, cn::as_stream(stream), A);
+    const dim3 grid(cn::grid_for(ntiles, 1, 256));
+    if (matrix_precision == CN_MATRIX_F16) {
+      if (pass_sem)
+        hipLaunchKernelGGL((cn::mf::field_backward_mfma_kernel<1, true>), grid, dim3(cn::mf::NT), cn::mf::LDS_BYTES,
+                           cn::as_stream(stream), A);
+      else
+        hipLaunchKernelGGL(cn::mf::field_backward_mfma_kernel<1>, grid, dim3(cn::mf::NT), cn::mf::LDS_BYTES,
+                           cn::as_stream(stream), A);
+    } else {
+      if (pass_sem)
+        hipLaunchKernelGGL((cn::mf::field_backward_mfma_kernel<0, true>), grid, dim3(cn::mf::NT), cn::mf::LDS_BYTES,
+                           cn::as_stream(stream), A);
+      else
+        hipLaunchKernelGGL(cn::mf::field_backward_mfma_kernel<0>, grid, dim3(cn::mf::NT), cn::mf::LDS_BYTES,
+                           cn::as_stream(stream), A);
+    }
     CN_DET_FLUSH(cn::as_stream(stream));  // (deterministic test build: the scratch records are floats again before the folds)
     cn::launch_coarse_reduce(A.coarse, A.grid, A.g.table, cn::as_stream(stream));
     cn::launch_cell_fold(A.cells, A.grid, A.g.table, cn::as_stream(stream));
@@ -1375,10 +1405,25 @@ extern "C" int cn_field_backward_general(const cn_field_params* params, const cn
                                          int64_t num_rays, int32_t num_samples, float* d_positions,
                                          float* d_directions, void* workspace, size_t workspace_bytes,
                                          cn_stream_t stream) {
+  return cn_field_backward_general_ex(params, grads, scene, app_mode, sh_unit_dir, app_mean, origins, directions, camera_indices,
+                                      starts, ends, d_density, d_rgb, d_semantics, num_rays, num_samples, d_positions,
+                                      d_directions, 0u, workspace, workspace_bytes, stream);
+}
+
+extern "C" int cn_field_backward_general_ex(const cn_field_params* params, const cn_field_params* grads,
+                                            const cn_scene* scene, int32_t app_mode, int32_t sh_unit_dir,
+                                            const float* app_mean, const float* origins, const float* directions,
+                                            const int64_t* camera_indices, const float* starts, const float* ends,
+                                            const float* d_density, const float* d_rgb, const float* d_semantics,
+                                            int64_t num_rays, int32_t num_samples, float* d_positions,
+                                            float* d_directions, uint32_t flags, void* workspace, size_t workspace_bytes,
+                                            cn_stream_t stream) {
   CN_REQUIRE(params && grads && scene && origins && directions && starts && ends && d_density && d_rgb && d_semantics,
              CN_ERR_INVALID, "cn_field_backward_general: null argument");
   CN_REQUIRE(app_mode != CN_APP_PER_CAMERA || camera_indices, CN_ERR_INVALID, "Camera indices are not provided.");
   CN_REQUIRE(app_mode != CN_APP_MEAN || app_mean, CN_ERR_INVALID, "cn_field_backward_general: app_mean required");
+  CN_REQUIRE((flags & ~cn::TRAIN_FLAGS_ALL) == 0, CN_ERR_INVALID, "cn_field_backward_general: unknown flags 0x%x",
+             (unsigned)flags);
   int rc = cn::validate_field(*params);
   if (rc) return rc;
   if ((rc = cn::validate_field(*grads))) return rc;
@@ -1475,6 +1520,7 @@ extern "C" int cn_field_backward_general(const cn_field_params* params, const cn
   A.d_dir = d_directions;
   A.R = num_rays;
   A.S = num_samples;
+  A.pass_sem = (flags & CN_TRAIN_PASS_SEMANTIC_GRADIENTS) ? 1 : 0;
   CN_REQUIRE(A.g_table && (!A.app_per_camera || A.g_emb), CN_ERR_INVALID, "cn_field_backward_general: null gradient buffer");
   // (the LDS need depends on the field shape, so the attribute is set per call: cheap, and correct on every device)
   CN_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(cn::gb::field_backward_general_kernel),

@@ -55,6 +55,7 @@ struct GenArgs {
   CoarseScatter coarse;  // private copies for level 0's gradient (cn_grid.scatter_scratch of the gradient grid)
   CellScatter cells;     // cell-major records of the coarse levels (take precedence for the levels they cover)
   int debug_skip;        // CN_DEBUG_SKIP, timing only: 1 no hash scatter, 4 no weight-gradient products, 64 no forward gathers
+  int pass_sem;          // CN_TRAIN_PASS_SEMANTIC_GRADIENTS: the semantic MLP's input gradient joins the geo rows of DG
 };
 
 __device__ __forceinline__ int opaque_i(int v) {
@@ -328,7 +329,8 @@ __global__ void __launch_bounds__(NTG) field_backward_general_kernel(GenArgs A) 
     __syncthreads();
     gen_fwd(A.col[2], C2, RGB, false, tid);
     __syncthreads();
-    // ---- semantic branch backward (stops at the detached geo features) ------------------------------------------------------
+    // ---- semantic branch backward (stops at the detached geo features; with pass_sem its input gradient W_s0^T d_s1 goes to
+    //      DG rows 0..geo-1, which nothing touches before the d(base output) assembly) ----------------------------------------
     {
       const float* sout = lds + A.r_s[A.ns - 1] * LDG;
       const int ht = lastsem.N;
@@ -351,6 +353,7 @@ __global__ void __launch_bounds__(NTG) field_backward_general_kernel(GenArgs A) 
         const float* xin = l == 0 ? G + LDG : lds + A.r_s[l - 1] * LDG;
         gen_dw(A.sem[l], dcur, xin, scratch, tid);
         if (l > 0) gen_bwd(A.sem[l], dcur, dnext, xin, tid);  // gate: the input is a post-ReLU activation
+        else if (A.pass_sem) gen_bwd(A.sem[0], dcur, DG, nullptr, tid);
         __syncthreads();
         float* t = dcur;
         dcur = dnext;
@@ -374,6 +377,13 @@ __global__ void __launch_bounds__(NTG) field_backward_general_kernel(GenArgs A) 
     gen_bwd(A.col[0], DB, DCIN, nullptr, tid);
     __syncthreads();
     // ---- d(base output): row 0 = density logit through trunc_exp and the selector, rows 1..geo from the colour input ----
+    // (with pass_sem plus the semantic MLP's share, which sits one row up in DG: read before anyone writes DG)
+    float dsem_lo = 0.f, dsem_hi = 0.f;  // rows grp and grp + 16
+    if (A.pass_sem) {  // (kernel-uniform)
+      dsem_lo = grp >= 1 && grp <= A.geo ? DG[(grp - 1) * LDG + s] : 0.f;
+      dsem_hi = grp + 16 <= A.geo ? DG[(grp + 15) * LDG + s] : 0.f;
+      __syncthreads();
+    }
     for (int row = grp; row < 32; row += 16) {
       float v = 0.f;
       if (row == 0) {
@@ -381,6 +391,7 @@ __global__ void __launch_bounds__(NTG) field_backward_general_kernel(GenArgs A) 
         v = dd * self * expf(fminf(fmaxf(G[s], -15.f), 15.f));
       } else if (row <= A.geo) {
         v = DCIN[(15 + row) * LDG + s];
+        if (A.pass_sem) v += row < 16 ? dsem_lo : dsem_hi;
       }
       DG[row * LDG + s] = v;
     }

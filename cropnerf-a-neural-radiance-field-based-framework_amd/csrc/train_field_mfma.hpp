@@ -16,6 +16,9 @@
 //   gather | h1 | o16 | s1 | s2 | d_s2 (+dW head) | d_s1 (+dW sem1) | c1 (+dW sem0) | c2 | rgb | d_c2 (+dW rgb) |
 //   d_c1 (+dW col1) | d_cin (+dW col0) | d_o16, embedding / SH gradients | d_h1 | d_enc (+dW base1) |
 //   hash scatter (+dW base0) | position gradient
+// PSG (template parameter, CN_TRAIN_PASS_SEMANTIC_GRADIENTS): the semantic MLP's input is not detached -- in the c1 phase two
+// waves also form W_s0^T d_s1 (the last reader of d_s1 before d_c1 overwrites it) and park it in the d_o16 rows, which the
+// d_o16 phase then adds the colour branch's geo gradient to.  The default instantiations (PSG = false) keep their code.
 #pragma once
 
 namespace cn {
@@ -257,7 +260,7 @@ __device__ __forceinline__ void flush_bias(float* g, int n0, f32x4 gb, int lane)
   }
 }
 
-template <int MM>
+template <int MM, bool PSG = false>
 __global__ void __launch_bounds__(NT) field_backward_mfma_kernel(FieldBwdArgs A) {
   extern __shared__ __align__(16) float lds[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -460,7 +463,7 @@ __global__ void __launch_bounds__(NT) field_backward_mfma_kernel(FieldBwdArgs A)
     }
     __syncthreads();
     __builtin_amdgcn_sched_barrier(0);
-    // ---- semantic branch (its input is the DETACHED geo: nothing flows back to the base MLP) ---------------------------
+    // ---- semantic branch (its input is the DETACHED geo unless PSG: then d_geo += W_s0^T d_s1, see the c1 phase) --------
     if (!(A.debug_skip & 32)) {  // (bit 32, timing only: the semantic branch's four phases skipped)
     store_blk<true>(A1, n0, s0, blk_fwd<16, MM>(Ws0, 20, n0, O16 + LDA, s0, bias4(lds + B_S0, n0, lane), lane), lane);
     __syncthreads();
@@ -485,6 +488,16 @@ __global__ void __launch_bounds__(NT) field_backward_mfma_kernel(FieldBwdArgs A)
     }
     // ---- colour branch -----------------------------------------------------------------------------------------------------
     if (wave < 4) gX = blk_dw<MM>(D1, 16 * wave, O16 + LDA, 0, gX, lane);                               // dW sem0
+    if (PSG && (wave == 4 || wave == 5)) {  // d_geo of the semantic MLP: geo input j -> DO16 row j + 1 (free until d_o16)
+      const int c0 = 16 * (wave - 4);
+      const f32x4 v = blk_bwd<64, MM>(Ws0, 20, 0, D1, c0, zero4, lane);
+      CN_LANE_IQ
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) {
+        const int k = 4 * q + rr;  // (column 15 of the padded W_s0 is zero: no row 16, which is DRGB's)
+        if (k < 15) DO16[(k + 1) * LDA + c0 + i] = v[rr];
+      }
+    }
     store_blk<true>(A1, n0, s0, blk_fwd<64, MM>(Wc0, 68, n0, CIN, s0, bias4(lds + B_C0, n0, lane), lane), lane);  // c1
     __syncthreads();
     __builtin_amdgcn_sched_barrier(0);
@@ -531,7 +544,8 @@ __global__ void __launch_bounds__(NT) field_backward_mfma_kernel(FieldBwdArgs A)
     }
     __syncthreads();
     __builtin_amdgcn_sched_barrier(0);
-    // ---- d_o16 (row 0: density logit through trunc_exp and the selector; rows 1..15: geo from the colour branch) -----
+    // ---- d_o16 (row 0: density logit through trunc_exp and the selector; rows 1..15: geo from the colour branch, plus the
+    //      semantic MLP's share parked there in the c1 phase when PSG) ------------------------------------------------------
     {
       const int row = lvl;  // 16 rows x 32 samples = one entry per thread
       float v;
@@ -540,6 +554,7 @@ __global__ void __launch_bounds__(NT) field_backward_mfma_kernel(FieldBwdArgs A)
         v = dd_in * self * expf(fminf(fmaxf(logit, -15.f), 15.f));
       } else {
         v = DCIN[(15 + row) * LDA + s];
+        if (PSG) v += DO16[row * LDA + s];
       }
       DO16[row * LDA + s] = v;
       b_o16 += v;

@@ -18,6 +18,9 @@ constexpr int TRAIN_MAX_S = 512;
 __device__ __forceinline__ float wave_total(float v) { return wave_read(wave_inclusive_scan(v), 63); }
 
 // one wave per ray.  LDS per wave: w[S] | P[S] (exclusive prefix of delta*sigma)
+// flags (kernel-uniform, CN_TRAIN_*): CN_TRAIN_PASS_SEMANTIC_GRADIENTS -- the semantic renderer's weights are not detached,
+// the semantic loss reaches the density through gw_i += gs s_i (fruit_nerf.py:586-590); CN_TRAIN_GRADIENT_SCALING -- nerfstudio's
+// scale_gradients_by_distance_squared (fruit_nerf.py:553-554): the three per-sample gradients times clamp(mid_i^2, 0, 1)
 __global__ void __launch_bounds__(256)
 train_render_backward_kernel(const float* __restrict__ starts, const float* __restrict__ ends,
                              const float* __restrict__ density, const float* __restrict__ rgb,
@@ -26,9 +29,10 @@ train_render_backward_kernel(const float* __restrict__ starts, const float* __re
                              float* __restrict__ out_rgb, float* __restrict__ out_sem, float* __restrict__ out_acc,
                              float* __restrict__ out_w, float* __restrict__ d_density, float* __restrict__ d_rgb,
                              float* __restrict__ d_sem, float* __restrict__ loss_sums,
-                             const float* __restrict__ spacing_bins) {
+                             const float* __restrict__ spacing_bins, unsigned flags) {
   extern __shared__ __align__(16) float lds[];
   const int wave = threadIdx.x >> 6, lane = lane_id();
+  const bool pass_sem = (flags & CN_TRAIN_PASS_SEMANTIC_GRADIENTS) != 0, scale = (flags & CN_TRAIN_GRADIENT_SCALING) != 0;
   float* wbuf = lds + wave * 2 * S;
   float* pbuf = wbuf + S;
   const long long waves = (long long)gridDim.x * 4;
@@ -109,7 +113,8 @@ train_render_backward_kernel(const float* __restrict__ starts, const float* __re
       const int ic = valid ? i : S - 1;
       const float w = valid ? wbuf[ic] : 0.f;
       const float c_r = rgb[3 * (base + ic) + 0], c_g = rgb[3 * (base + ic) + 1], c_b = rgb[3 * (base + ic) + 2];
-      const float gw = G0 * (c_r - lr_) + G1 * (c_g - lg_) + G2 * (c_b - lb_);
+      float gw = G0 * (c_r - lr_) + G1 * (c_g - lg_) + G2 * (c_b - lb_);
+      if (pass_sem) gw = fmaf(gs, sem[base + ic], gw);  // (no background term: the semantic renderer blends none)
       const float term = valid ? gw * w : 0.f;
       const float incl = wave_inclusive_scan(term);
       const float later = suffix + (incl - term);  // strictly later samples
@@ -117,12 +122,22 @@ train_render_backward_kernel(const float* __restrict__ starts, const float* __re
       if (valid) {
         const float T = expf(-pbuf[ic]);
         const float delta = ends[base + ic] - starts[base + ic];
-        d_density[base + ic] = delta * (gw * (T - w) - later);
         const float k = (ic == S - 1) ? w + (1.f - acc) : w;
-        d_rgb[3 * (base + ic) + 0] = G0 * k;
-        d_rgb[3 * (base + ic) + 1] = G1 * k;
-        d_rgb[3 * (base + ic) + 2] = G2 * k;
-        d_sem[base + ic] = gs * w;
+        if (scale) {  // (the bins are detached: the factor is a constant of the backward)
+          const float m = (starts[base + ic] + ends[base + ic]) / 2.f;
+          const float f = fminf(m * m, 1.f);
+          d_density[base + ic] = delta * (gw * (T - w) - later) * f;
+          d_rgb[3 * (base + ic) + 0] = G0 * k * f;
+          d_rgb[3 * (base + ic) + 1] = G1 * k * f;
+          d_rgb[3 * (base + ic) + 2] = G2 * k * f;
+          d_sem[base + ic] = gs * w * f;
+        } else {
+          d_density[base + ic] = delta * (gw * (T - w) - later);
+          d_rgb[3 * (base + ic) + 0] = G0 * k;
+          d_rgb[3 * (base + ic) + 1] = G1 * k;
+          d_rgb[3 * (base + ic) + 2] = G2 * k;
+          d_sem[base + ic] = gs * w;
+        }
       }
     }
     __builtin_amdgcn_wave_barrier();
@@ -588,9 +603,23 @@ extern "C" int cn_train_render_backward(const float* starts, const float* ends, 
                                         float* out_accumulation, float* out_weights, float* d_density, float* d_rgb,
                                         float* d_semantics, float* loss_sums, const float* spacing_bins,
                                         cn_stream_t stream) {
+  return cn_train_render_backward_ex(starts, ends, density, rgb, semantics, image, fruit_mask, num_rays, num_samples,
+                                     semantic_loss_weight, out_rgb, out_semantics, out_accumulation, out_weights, d_density,
+                                     d_rgb, d_semantics, loss_sums, spacing_bins, 0u, stream);
+}
+
+extern "C" int cn_train_render_backward_ex(const float* starts, const float* ends, const float* density,
+                                           const float* rgb, const float* semantics, const float* image,
+                                           const float* fruit_mask, int64_t num_rays, int32_t num_samples,
+                                           float semantic_loss_weight, float* out_rgb, float* out_semantics,
+                                           float* out_accumulation, float* out_weights, float* d_density, float* d_rgb,
+                                           float* d_semantics, float* loss_sums, const float* spacing_bins,
+                                           uint32_t flags, cn_stream_t stream) {
   CN_REQUIRE(starts && ends && density && rgb && semantics && image && fruit_mask && d_density && d_rgb &&
                  d_semantics && loss_sums,
              CN_ERR_INVALID, "cn_train_render_backward: null argument");
+  CN_REQUIRE((flags & ~cn::TRAIN_FLAGS_ALL) == 0, CN_ERR_INVALID, "cn_train_render_backward: unknown flags 0x%x",
+             (unsigned)flags);
   CN_REQUIRE(num_samples >= 1 && num_samples <= cn::TRAIN_MAX_S, CN_ERR_UNSUPPORTED,
              "cn_train_render_backward: %d samples per ray (max %d)", num_samples, cn::TRAIN_MAX_S);
   if (num_rays <= 0) return CN_OK;
@@ -598,7 +627,7 @@ extern "C" int cn_train_render_backward(const float* starts, const float* ends, 
   hipLaunchKernelGGL(cn::train_render_backward_kernel, dim3(cn::grid_for(num_rays, 4, 4096)), dim3(256), lds,
                      cn::as_stream(stream), starts, ends, density, rgb, semantics, image, fruit_mask,
                      (long long)num_rays, num_samples, semantic_loss_weight, out_rgb, out_semantics, out_accumulation,
-                     out_weights, d_density, d_rgb, d_semantics, loss_sums, spacing_bins);
+                     out_weights, d_density, d_rgb, d_semantics, loss_sums, spacing_bins, (unsigned)flags);
   if (int rc = cn::check_launch("cn_train_render_backward")) return rc;
   CN_DET_FLUSH(cn::as_stream(stream));
   return CN_OK;

@@ -15,6 +15,10 @@ step < 10``.  No GradScaler: exact fp32 by default; ``config.matrix_precision = 
 mixed-precision class for the field (fp16 forward operands, bf16 gradient products, fp32 sums and master parameters:
 ``FruitModel.train_matrix_precision``), whose bf16 deltas need no loss scale.
 
+``pass_semantic_gradients`` / ``use_gradient_scaling`` (``FruitNerfModelConfig``, both off by default) change only the
+gradients of the iteration: they become the ``CN_TRAIN_*`` flags of the render and field backward kernels
+(``FruitTrainer.train_flags``).
+
 An optimiser group is stepped only when the iteration produced a gradient for it: on the iterations where the proposal
 networks are evaluated under ``no_grad`` their parameters have ``grad is None`` in the reference, ``torch.optim.Adam``
 skips them (moments, per-parameter step count and weights untouched) -- the learning-rate schedules advance every
@@ -67,6 +71,12 @@ def groups_from_spec(optimizers) -> Dict[str, "OptimGroup"]:
 
 
 class FruitTrainer:
+    """The training iteration of one ``FruitModel`` (see the module docstring).
+
+    ``train_flags`` (``L.TRAIN_PASS_SEMANTIC_GRADIENTS`` | ``L.TRAIN_GRADIENT_SCALING``) are derived from the model config ONCE,
+    here, and stay fixed for the trainer's life: a captured HIP graph of the iteration holds them as kernel arguments, so
+    changing ``pass_semantic_gradients`` / ``use_gradient_scaling`` afterwards takes a new trainer."""
+
     def __init__(self, model: FruitModel, groups: Optional[Dict[str, OptimGroup]] = None, seed: int = 0):
         self.model = model
         if model.config.background_color != "last_sample":
@@ -77,6 +87,10 @@ class FruitTrainer:
         # fruit_nerf_method_big / _huge field shapes train through the shape-generic kernels (cn_field_eval +
         # cn_field_backward_general)
         self.general = not model._fused_shape
+        # the semantic loss through the weights and the geo features (fruit_nerf.py:586-590, fruit_field.py:264-266) and
+        # nerfstudio's distance-squared gradient scaling (fruit_nerf.py:553-554): flags of the backward kernels, fixed from here on
+        self.train_flags = ((L.TRAIN_PASS_SEMANTIC_GRADIENTS if model.config.pass_semantic_gradients else 0)
+                            | (L.TRAIN_GRADIENT_SCALING if model.config.use_gradient_scaling else 0))
         # the proposal sampler of the training forward as ONE launch (cn_proposal_sample_train) when the proposal networks
         # have the shapes it is built for; CN_TRAIN_FUSED_SAMPLER=0 composes the materialising calls instead (A/B, tests)
         self.fused_sampler = os.environ.get("CN_TRAIN_FUSED_SAMPLER", "1") != "0"
@@ -274,7 +288,7 @@ class FruitTrainer:
         # (with the final level's spacing bins: get_metrics_dict's distortion, fruit_nerf.py:643, rides in the same kernel -- its
         #  sum over rays goes to loss_sums[4], the epilogue divides)
         rb_out = ops.train_render_backward(starts, ends, fo["density"], fo["rgb"], fo["semantics"], image, mask,
-                                           cfg.semantic_loss_weight, self.loss_sums, spacing_bins=bins)
+                                           cfg.semantic_loss_weight, self.loss_sums, spacing_bins=bins, flags=self.train_flags)
         # The three backward passes (field, proposal network 0, proposal network 1) only share read-only inputs, so they run
         # on three streams when self.concurrent_backward: each is bound by the float-atomic request rate of its scatter for
         # part of its time and by matrix / gather work for the rest, and the parts of different kernels overlap on a CU.
@@ -285,12 +299,12 @@ class FruitTrainer:
                 self._general_ws = ops.field_backward_general(
                     m.field, self.grad_field, scene, o, d, cam, starts, ends, rb_out["d_density"], rb_out["d_rgb"],
                     rb_out["d_semantics"], app_mode=L.APP_PER_CAMERA, sh_unit_dir=cfg.sh_input == "unit",
-                    workspace=self._general_ws, d_positions=dpos, d_directions=ddir)
+                    workspace=self._general_ws, d_positions=dpos, d_directions=ddir, flags=self.train_flags)
             else:
                 ops.field_backward(m.field, self.grad_field, scene, o, d, cam, starts, ends, rb_out["d_density"],
                                    rb_out["d_rgb"], rb_out["d_semantics"], app_mode=L.APP_PER_CAMERA,
                                    sh_unit_dir=cfg.sh_input == "unit", d_positions=dpos, d_directions=ddir,
-                                   matrix_precision=mp)
+                                   matrix_precision=mp, flags=self.train_flags)
             if self.train_pose:
                 ops.ray_backward(dpos, ddir, starts, ends, d_o_acc, d_d_acc)
 

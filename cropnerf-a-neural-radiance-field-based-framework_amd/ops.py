@@ -794,9 +794,10 @@ def pointcloud_compact_calls(origins: Tensor, directions: Tensor, depth: Tensor,
 
 def train_render_backward(starts: Tensor, ends: Tensor, density: Tensor, rgb: Tensor, semantics: Tensor,
                           image: Tensor, fruit_mask: Tensor, semantic_loss_weight: float, loss_sums: Tensor,
-                          spacing_bins: Optional[Tensor] = None) -> Dict[str, Tensor]:
+                          spacing_bins: Optional[Tensor] = None, flags: int = 0) -> Dict[str, Tensor]:
     """cn_train_render_backward: rendered values, per-sample gradients of rgb_loss + semantics_loss.  ``spacing_bins`` [R, S+1]:
-    the distortion metric's sum over rays is added to ``loss_sums[4]`` as well (``loss_sums`` has five slots then)."""
+    the distortion metric's sum over rays is added to ``loss_sums[4]`` as well (``loss_sums`` has five slots then).
+    ``flags``: ``L.TRAIN_*`` bits (``cn_train_render_backward_ex``): pass_semantic_gradients / use_gradient_scaling."""
     lib = L.load()
     R, S = starts.shape
     dev = starts.device
@@ -806,12 +807,12 @@ def train_render_backward(starts: Tensor, ends: Tensor, density: Tensor, rgb: Te
            "accumulation": torch.empty(R, 1, device=dev), "weights": torch.empty(R, S, device=dev),
            "d_density": torch.empty(R, S, device=dev), "d_rgb": torch.empty(R, S, 3, device=dev),
            "d_semantics": torch.empty(R, S, device=dev)}
-    L.check(lib.cn_train_render_backward(
+    L.check(lib.cn_train_render_backward_ex(
         _p(_f32(starts, "starts")), _p(_f32(ends, "ends")), _p(_f32(density, "density")), _p(_f32(rgb, "rgb")),
         _p(_f32(semantics, "semantics")), _p(_f32(image, "image")), _p(_f32(fruit_mask, "fruit_mask")), R, S,
         float(semantic_loss_weight), _p(out["rgb"]), _p(out["semantics"]), _p(out["accumulation"]), _p(out["weights"]),
         _p(out["d_density"]), _p(out["d_rgb"]), _p(out["d_semantics"]), _p(_f32(loss_sums, "loss_sums")),
-        _p(_f32(spacing_bins, "spacing_bins")), _stream(starts)))
+        _p(_f32(spacing_bins, "spacing_bins")), int(flags), _stream(starts)))
     return out
 
 
@@ -858,22 +859,24 @@ def field_backward(fh: FieldHandle, gh: FieldHandle, scene: L.Scene, origins: Te
                    camera_indices: Optional[Tensor], starts: Tensor, ends: Tensor, d_density: Tensor, d_rgb: Tensor,
                    d_semantics: Tensor, app_mode: int = L.APP_PER_CAMERA, sh_unit_dir: bool = True,
                    app_mean: Optional[Tensor] = None, d_positions: Optional[Tensor] = None,
-                   d_directions: Optional[Tensor] = None, matrix_precision: int = L.MATRIX_FP32) -> None:
+                   d_directions: Optional[Tensor] = None, matrix_precision: int = L.MATRIX_FP32, flags: int = 0) -> None:
     """Accumulates parameter gradients into the tensors behind ``gh`` (a FieldHandle over the gradient dict).
     ``d_positions`` / ``d_directions`` [R,S,3] (optional) are overwritten with the per-sample position / SH-direction
     gradients that feed the camera pose refinement.  ``matrix_precision``: ``MATRIX_F16`` = the reference's mixed-precision
-    class (fp16 forward recompute, bf16 gradient products, fp32 sums: ``cn_field_backward_mp``)."""
+    class (fp16 forward recompute, bf16 gradient products, fp32 sums: ``cn_field_backward_mp``).  ``flags``: ``L.TRAIN_*`` bits
+    (``cn_field_backward_ex``; ``TRAIN_PASS_SEMANTIC_GRADIENTS`` lets the semantic loss reach the base MLP and the table)."""
     lib = L.load()
     R, S = starts.shape
     for t, nm in ((d_positions, "d_positions"), (d_directions, "d_directions")):
         if t is not None and tuple(t.shape) != (R, S, 3):
             raise ValueError(f"{nm} must be [{R},{S},3]")
-    L.check(lib.cn_field_backward_mp(
+    L.check(lib.cn_field_backward_ex(
         C.byref(fh.struct), C.byref(gh.struct), C.byref(scene), app_mode, 1 if sh_unit_dir else 0,
         _p(_f32(app_mean, "app_mean")), _p(_f32(origins, "origins")), _p(_f32(directions, "directions")),
         _p(_i64(camera_indices, "camera_indices")), _p(_f32(starts, "starts")), _p(_f32(ends, "ends")),
         _p(_f32(d_density, "d_density")), _p(_f32(d_rgb, "d_rgb")), _p(_f32(d_semantics, "d_semantics")), R, S,
-        _p(_f32(d_positions, "d_positions")), _p(_f32(d_directions, "d_directions")), int(matrix_precision), _stream(starts)))
+        _p(_f32(d_positions, "d_positions")), _p(_f32(d_directions, "d_directions")), int(matrix_precision),
+        int(flags), _stream(starts)))
 
 
 def field_backward_general(fh: FieldHandle, gh: FieldHandle, scene: L.Scene, origins: Tensor, directions: Tensor,
@@ -881,20 +884,21 @@ def field_backward_general(fh: FieldHandle, gh: FieldHandle, scene: L.Scene, ori
                            d_rgb: Tensor, d_semantics: Tensor, app_mode: int = L.APP_PER_CAMERA,
                            sh_unit_dir: bool = True, app_mean: Optional[Tensor] = None,
                            workspace: Optional[Tensor] = None, d_positions: Optional[Tensor] = None,
-                           d_directions: Optional[Tensor] = None) -> Tensor:
+                           d_directions: Optional[Tensor] = None, flags: int = 0) -> Tensor:
     """``cn_field_backward_general``: parameter gradients for any field shape of the reference's configs (accumulated
-    into the tensors behind ``gh``).  Returns the workspace so the caller can reuse it."""
+    into the tensors behind ``gh``).  Returns the workspace so the caller can reuse it.  ``flags`` as for
+    ``field_backward`` (``cn_field_backward_general_ex``)."""
     lib = L.load()
     R, S = starts.shape
     need = lib.cn_field_backward_general_workspace_bytes(C.byref(fh.struct))
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty(need, dtype=torch.uint8, device=starts.device)
-    L.check(lib.cn_field_backward_general(
+    L.check(lib.cn_field_backward_general_ex(
         C.byref(fh.struct), C.byref(gh.struct), C.byref(scene), app_mode, 1 if sh_unit_dir else 0,
         _p(_f32(app_mean, "app_mean")), _p(_f32(origins, "origins")), _p(_f32(directions, "directions")),
         _p(_i64(camera_indices, "camera_indices")), _p(_f32(starts, "starts")), _p(_f32(ends, "ends")),
         _p(_f32(d_density, "d_density")), _p(_f32(d_rgb, "d_rgb")), _p(_f32(d_semantics, "d_semantics")), R, S,
-        _p(_f32(d_positions, "d_positions")), _p(_f32(d_directions, "d_directions")),
+        _p(_f32(d_positions, "d_positions")), _p(_f32(d_directions, "d_directions")), int(flags),
         C.c_void_p(workspace.data_ptr()), workspace.numel(), _stream(starts)))
     return workspace
 

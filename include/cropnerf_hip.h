@@ -60,6 +60,17 @@ typedef void* cn_stream_t; /* hipStream_t */
 #define CN_BG_LAST_SAMPLE 0
 #define CN_BG_COLOR 1
 
+/* training switches of FruitNerfModelConfig (flags of the *_ex training entry points; 0 = the defaults, both off).  They change
+ * the gradients of the training iteration only, never a forward value.
+ * CN_TRAIN_PASS_SEMANTIC_GRADIENTS: pass_semantic_gradients=True -- the semantic MLP reads the geo features and the semantic
+ *   renderer the weights WITHOUT detaching them (fruit_field.py:264-266, fruit_nerf.py:586-590): the semantic loss reaches the
+ *   density (render backward) and, through the geo features, the base MLP, the hash table and the positions (field backward).
+ * CN_TRAIN_GRADIENT_SCALING: nerfacto's use_gradient_scaling=True -- nerfstudio's scale_gradients_by_distance_squared on the
+ *   field outputs (fruit_nerf.py:553-554): the gradients of sample i's density, rgb and semantics times
+ *   clamp(((start_i + end_i) / 2)^2, 0, 1).  Render backward only; the field backward kernels take the scaled gradients. */
+#define CN_TRAIN_PASS_SEMANTIC_GRADIENTS 1u
+#define CN_TRAIN_GRADIENT_SCALING 2u
+
 /* Hash-grid layouts.  The reference builds FruitField with implementation="tcnn" by default (fruit_nerf/fruit_field.py:95,
  * 125-132) and falls back to nerfstudio's torch HashEncoding with implementation="torch"; the two differ in indexing.
  *   CN_GRID_TORCH  nerfstudio torch HashEncoding: every level hashed into 2^log2_table_size entries, level l at entry
@@ -522,7 +533,8 @@ int cn_embedding_mean(const float* embedding, int32_t num_images, int32_t dim, f
 
 /* Forward + backward of the volume renderer and of the rgb (MSE over R*3) and semantics
  * (semantic_loss_weight * BCE-with-logits mean over R) losses, training mode (no clamp, "last_sample"
- * background, semantics rendered with detached weights: fruit_nerf.py:556-591).  Inputs per sample [R,S]:
+ * background, semantics rendered with detached weights unless CN_TRAIN_PASS_SEMANTIC_GRADIENTS: fruit_nerf.py:556-591).
+ * Inputs per sample [R,S]:
  * starts, ends, density, rgb [R,S,3], semantics.  Outputs: rendered rgb [R,3] / semantics [R,1] /
  * accumulation [R,1] / weights [R,S] (any NULL skips), gradients d_density [R,S], d_rgb [R,S,3],
  * d_semantics [R,S] of (rgb_loss + semantics_loss), and loss_sums[0] += sum (rgb-image)^2,
@@ -536,6 +548,15 @@ int cn_train_render_backward(const float* starts, const float* ends, const float
                              float semantic_loss_weight, float* out_rgb, float* out_semantics,
                              float* out_accumulation, float* out_weights, float* d_density, float* d_rgb,
                              float* d_semantics, float* loss_sums, const float* spacing_bins, cn_stream_t stream);
+/* The same with training switches (CN_TRAIN_* bits; cn_train_render_backward = flags 0): CN_TRAIN_PASS_SEMANTIC_GRADIENTS adds
+ * the semantic loss's share to d_density, CN_TRAIN_GRADIENT_SCALING scales d_density / d_rgb / d_semantics per sample.  The
+ * rendered values, weights and loss sums do not depend on the flags. */
+int cn_train_render_backward_ex(const float* starts, const float* ends, const float* density, const float* rgb,
+                                const float* semantics, const float* image, const float* fruit_mask, int64_t num_rays,
+                                int32_t num_samples, float semantic_loss_weight, float* out_rgb, float* out_semantics,
+                                float* out_accumulation, float* out_weights, float* d_density, float* d_rgb,
+                                float* d_semantics, float* loss_sums, const float* spacing_bins, uint32_t flags,
+                                cn_stream_t stream);
 
 /* nerfstudio interlevel_loss term of ONE proposal level (fruit_nerf.py:609-612): final spacing bins
  * [R,Sf+1] and (detached) final weights [R,Sf] against the level's spacing bins [R,Sp+1] and density
@@ -561,7 +582,7 @@ int cn_interlevel_backward_levels(const float* final_spacing_bins, const float* 
                                   float loss_mult, float* loss_sum, cn_stream_t stream);
 
 /* Parameter gradients of FruitField (training branch: per-camera appearance, semantic MLP on detached geo
- * features, fruit_nerf/fruit_field.py:235-282) from per-sample upstream gradients; the forward is recomputed
+ * features -- not detached under CN_TRAIN_PASS_SEMANTIC_GRADIENTS of the _ex forms -- fruit_nerf/fruit_field.py:235-282) from per-sample upstream gradients; the forward is recomputed
  * tile by tile.  app_mean [app_dim] is read with CN_APP_MEAN only.  d_positions / d_directions (optional) receive
  * d loss / d (world sample position) and d loss / d (ray direction, through the SH colour input) per sample -- the
  * inputs of the camera pose refinement's backward (the positions get `requires_grad`, fruit_field.py:181-184). */
@@ -583,6 +604,17 @@ int cn_field_backward_mp(const cn_field_params* params, const cn_field_params* g
                          const float* ends, const float* d_density, const float* d_rgb, const float* d_semantics,
                          int64_t num_rays, int32_t num_samples, float* d_positions, float* d_directions,
                          int32_t matrix_precision, cn_stream_t stream);
+/* The same with training switches (CN_TRAIN_* bits; cn_field_backward_mp = flags 0).  CN_TRAIN_PASS_SEMANTIC_GRADIENTS: the
+ * semantic MLP's input gradient joins the colour branch's geo gradient ahead of the base-MLP backward, so the semantic loss
+ * reaches the base MLP, the hash table and d_positions.  CN_TRAIN_GRADIENT_SCALING is accepted and needs nothing here (the
+ * upstream gradients arrive scaled).  The scalar A/B implementation (CN_FIELD_BACKWARD_IMPL=scalar) refuses
+ * CN_TRAIN_PASS_SEMANTIC_GRADIENTS with CN_ERR_UNSUPPORTED. */
+int cn_field_backward_ex(const cn_field_params* params, const cn_field_params* grads, const cn_scene* scene,
+                         int32_t app_mode, int32_t sh_unit_dir, const float* app_mean, const float* origins,
+                         const float* directions, const int64_t* camera_indices, const float* starts,
+                         const float* ends, const float* d_density, const float* d_rgb, const float* d_semantics,
+                         int64_t num_rays, int32_t num_samples, float* d_positions, float* d_directions,
+                         int32_t matrix_precision, uint32_t flags, cn_stream_t stream);
 
 /* The same for the other field shapes of the reference's method configs (fruit_nerf_method_big / _huge:
  * fruit_nerf/fruit_nerf_config.py:66-172): base MLP 2 layers, semantic MLP 2-3 layers, colour MLP 3 layers, widths
@@ -596,6 +628,14 @@ int cn_field_backward_general(const cn_field_params* params, const cn_field_para
                               const float* d_semantics, int64_t num_rays, int32_t num_samples,
                               float* d_positions /*[R,S,3] or NULL*/, float* d_directions /*[R,S,3] or NULL*/,
                               void* workspace, size_t workspace_bytes, cn_stream_t stream);
+/* The same with training switches (CN_TRAIN_* bits, as for cn_field_backward_ex; cn_field_backward_general = flags 0). */
+int cn_field_backward_general_ex(const cn_field_params* params, const cn_field_params* grads, const cn_scene* scene,
+                                 int32_t app_mode, int32_t sh_unit_dir, const float* app_mean, const float* origins,
+                                 const float* directions, const int64_t* camera_indices, const float* starts,
+                                 const float* ends, const float* d_density, const float* d_rgb,
+                                 const float* d_semantics, int64_t num_rays, int32_t num_samples, float* d_positions,
+                                 float* d_directions, uint32_t flags, void* workspace, size_t workspace_bytes,
+                                 cn_stream_t stream);
 
 /* Parameter gradients of one proposal network from d loss / d density [R,S]; d_positions as above. */
 int cn_proposal_backward(const cn_density_params* params, const cn_density_params* grads, const cn_scene* scene,

@@ -1,5 +1,6 @@
 """Times the default fruit_nerf training iteration (TRAIN_RAYS random rays, default 4096) on cuda:0; CN_DEBUG_SKIP ablates parts of
-cn_field_backward (1 hash atomics, 2 embedding atomics, 4 weight-gradient dots).  Profiling aid, not a test."""
+cn_field_backward (1 hash atomics, 2 embedding atomics, 4 weight-gradient dots).  TRAIN_PASS_SEM=1 / TRAIN_GRAD_SCALING=1 turn
+on pass_semantic_gradients / use_gradient_scaling (their cost against the default iteration).  Profiling aid, not a test."""
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cropnerf_amd import config as PC, ops, synthetic
@@ -9,7 +10,9 @@ from cropnerf_amd.rays import RayBundle, SceneBox, Cameras
 dev = "cuda"
 cfg = PC.FruitNerfModelConfig(log2_hashmap_size=int(os.environ.get("LOG2_T", "19")),
                               num_nerf_samples_per_ray=int(os.environ.get("TRAIN_FIELD_SAMPLES", "48")),
-                              matrix_precision=os.environ.get("TRAIN_MATRIX", "fp32"))  # "f16": the mixed-precision iteration
+                              matrix_precision=os.environ.get("TRAIN_MATRIX", "fp32"),  # "f16": the mixed-precision iteration
+                              pass_semantic_gradients=os.environ.get("TRAIN_PASS_SEM", "0") == "1",
+                              use_gradient_scaling=os.environ.get("TRAIN_GRAD_SCALING", "0") == "1")
 fspec = cfg.field_spec(100)
 params = synthetic.p_rand(fspec, cfg.proposal_specs(), seed=0, device=dev)
 model = FruitModel(cfg, SceneBox(torch.tensor([[-1.0,-1,-1],[1,1,1]])), 100, {"semantics": Semantics()}, device=dev, params=params)
@@ -38,4 +41,4 @@ if os.environ.get("PER_ITER") == "1":  # one line per iteration, each waited for
 for i in range(WARM): tr.train_iteration(rb, batch)
 torch.cuda.synchronize(); t=time.perf_counter()
 for i in range(ITERS): tr.train_iteration(rb, batch)
-torch.cuda.synchronize(); print("CN_DEBUG_SKIP", os.environ.get("CN_DEBUG_SKIP"), "rays", R, "ms/iter", (time.perf_counter()-t)/ITERS*1e3)
+torch.cuda.synchronize(); print("CN_DEBUG_SKIP", os.environ.get("CN_DEBUG_SKIP"), "flags", tr.train_flags, "rays", R, "ms/iter", (time.perf_counter()-t)/ITERS*1e3)
