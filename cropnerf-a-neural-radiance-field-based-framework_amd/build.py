@@ -53,7 +53,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     BUILD.mkdir(exist_ok=True)
     headers = _headers()
     flags = ["-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-x", "hip", "-Wno-unused-result"]
-    flags += os.environ.get("CN_EXTRA_HIPCC_FLAGS", "").split()  # e.g. -DCN_FUSED_PIPELINE=0 for A/B builds
+    flags += os.environ.get("CN_EXTRA_HIPCC_FLAGS", "").split()  # e.g. -DCN_ABLATE_GATHER=1 for timing-only builds
     jobs = []
     objs = []
     det_objs = []  # the test library: the training units compiled with the macro, every other object shared

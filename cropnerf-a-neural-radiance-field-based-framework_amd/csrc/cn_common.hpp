@@ -393,66 +393,32 @@ __device__ __forceinline__ XpLoads<HALF> hash_level_xpair_issue(const void* __re
   }
   return L;
 }
-#ifndef CN_XPAIR_WEIGHT_SWAP
-#define CN_XPAIR_WEIGHT_SWAP 1
-#endif
+// Which entry of an aligned pair is the lower-x corner depends on the row's hash parity; instead of SELECTING the values (six
+// conditional moves per row: lo / hi of two features, and the separately loaded upper corner of odd cells) the x WEIGHTS are
+// selected -- row value = a wa + b wb + u ox with (wa, wb) = (mx, ox') or (ox', mx), ox' = 0 for odd cells (their upper corner
+// is u; u is zero for even cells): two conditional moves per row and one more packed multiply-add.
 template <bool HALF = false>
 __device__ __forceinline__ float2 hash_level_xpair_blend(const XpLoads<HALF>& L) {
   const bool odd = (L.bits & 16u) != 0u;
-#if CN_XPAIR_WEIGHT_SWAP
-  // Which entry of an aligned pair is the lower-x corner depends on the row's hash parity; instead of SELECTING the values (six
-  // conditional moves per row: lo / hi of two features, and the separately loaded upper corner of odd cells) the x WEIGHTS are
-  // selected -- row value = a wa + b wb + u ox with (wa, wb) = (mx, ox') or (ox', mx), ox' = 0 for odd cells (their upper corner
-  // is u; u is zero for even cells): two conditional moves per row and one more packed multiply-add.
-  {
-    typedef float v2f __attribute__((ext_vector_type(2)));
-    const float ox = L.ox, oy = L.oy, oz = L.oz;
-    const float mx = 1.f - ox, my = 1.f - oy, mz = 1.f - oz;
-    const float oxe = odd ? 0.f : ox;
-    v2f row[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const bool second = ((L.bits >> r) & 1u) != 0u;
-      const float wa = second ? oxe : mx, wb = second ? mx : oxe;
-      v2f a, b, u;
-      a.x = (float)L.pr[r].x;
-      a.y = (float)L.pr[r].y;
-      b.x = (float)L.pr[r].z;
-      b.y = (float)L.pr[r].w;
-      u.x = (float)L.up[r].x;
-      u.y = (float)L.up[r].y;
-      row[r] = u * ox + (b * wb + a * wa);
-    }
-    const v2f a2 = row[3] * oy + row[2] * my, b2 = row[1] * oy + row[0] * my;
-    const v2f rv = a2 * oz + b2 * mz;
-    float2 r;
-    r.x = rv.x;
-    r.y = rv.y;
-    asm volatile("" : "+v"(r.x), "+v"(r.y));
-    return r;
-  }
-#endif
-  float2 lo[4], hi[4];
+  typedef float v2f __attribute__((ext_vector_type(2)));
+  const float ox = L.ox, oy = L.oy, oz = L.oz;
+  const float mx = 1.f - ox, my = 1.f - oy, mz = 1.f - oz;
+  const float oxe = odd ? 0.f : ox;
+  v2f row[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const bool second = ((L.bits >> r) & 1u) != 0u;
-    const float2 a = make_float2((float)L.pr[r].x, (float)L.pr[r].y), b = make_float2((float)L.pr[r].z, (float)L.pr[r].w);
-    const float2 u = make_float2((float)L.up[r].x, (float)L.up[r].y);
-    lo[r] = second ? b : a;
-    hi[r] = odd ? u : (second ? a : b);  // the other entry of the pair is the upper-x corner when x is even
+    const float wa = second ? oxe : mx, wb = second ? mx : oxe;
+    v2f a, b, u;
+    a.x = (float)L.pr[r].x;
+    a.y = (float)L.pr[r].y;
+    b.x = (float)L.pr[r].z;
+    b.y = (float)L.pr[r].w;
+    u.x = (float)L.up[r].x;
+    u.y = (float)L.up[r].y;
+    row[r] = u * ox + (b * wb + a * wa);
   }
-  const float ox = L.ox, oy = L.oy, oz = L.oz;
-  const float mx = 1.f - ox, my = 1.f - oy, mz = 1.f - oz;
-  typedef float v2f __attribute__((ext_vector_type(2)));
-  auto V = [](float2 t) {
-    v2f v;
-    v.x = t.x;
-    v.y = t.y;
-    return v;
-  };
-  const v2f f03 = V(hi[3]) * ox + V(lo[3]) * mx, f12 = V(hi[2]) * ox + V(lo[2]) * mx;
-  const v2f f56 = V(hi[0]) * ox + V(lo[0]) * mx, f47 = V(hi[1]) * ox + V(lo[1]) * mx;
-  const v2f a2 = f03 * oy + f12 * my, b2 = f47 * oy + f56 * my;
+  const v2f a2 = row[3] * oy + row[2] * my, b2 = row[1] * oy + row[0] * my;
   const v2f rv = a2 * oz + b2 * mz;
   float2 r;
   r.x = rv.x;
@@ -698,11 +664,7 @@ typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x2p __attribute__((ext_vector_type(2)));
 struct PkLoads {
   u32x2p pr[4];    // the aligned pair holding the lower-x corner of rows (y, z) = ff, cf, fc, cc
-#ifdef CN_PK_UP_WIDE
-  u32x2p up[4];    // odd x index: the aligned pair that holds the upper-x corner (its first entry: x + 1 is even)
-#else
   unsigned up[4];  // the upper-x corner of each row, loaded separately when the x index is odd
-#endif
   unsigned bits;   // bit r: the lower-x corner is the pair's second entry; bit 4: odd x index
   unsigned wxy, wzz;  // interpolation weights as packed fp16 pairs (x, y) and (z, z)
 };
@@ -727,22 +689,13 @@ __device__ __forceinline__ PkLoads hash_level_pk_issue(const void* __restrict__ 
     const unsigned x = k.hx0 ^ hyz[r];
     L.bits |= (x & 1u) << r;
     L.pr[r] = *reinterpret_cast<const u32x2p*>(base + (size_t)(((x & pair_mask) + lv.off) << 2));
-#ifdef CN_PK_UP_WIDE
-    L.up[r] = u32x2p{0u, 0u};
-#else
     L.up[r] = 0u;
-#endif
   }
 #if !defined(CN_ABLATE_X1)  // timing-only build: no second load
   if (odd) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-#ifdef CN_PK_UP_WIDE  // 8-byte loads coalesce lane PAIRS (4-byte loads only whole quads): worth it when neighbouring lanes are
-                      // neighbouring pixels
-      L.up[r] = *reinterpret_cast<const u32x2p*>(base + (size_t)((((k.hx1 ^ hyz[r]) & pair_mask) + lv.off) << 2));
-#else
       L.up[r] = *reinterpret_cast<const unsigned*>(base + (size_t)((((k.hx1 ^ hyz[r]) & lv.mask) + lv.off) << 2));
-#endif
     }
   }
 #endif
@@ -756,13 +709,7 @@ __device__ __forceinline__ unsigned hash_level_pk_blend(const PkLoads& L) {
     const bool second = (L.bits & (1u << r)) != 0u;
     const unsigned a = L.pr[r].x, b = L.pr[r].y;
     lo[r] = __builtin_bit_cast(f16x2, second ? b : a);
-#ifdef CN_PK_UP_WIDE
-    // x + 1 is even: the upper corner's entry index has the parity of (x ^ y-term ^ z-term) ^ 1, i.e. it is the pair's
-    // second entry exactly when the lower corner (odd x) was its pair's FIRST
-    const unsigned upv = second ? L.up[r].x : L.up[r].y;
-#else
-    const unsigned upv = L.up[r];
-#endif
+    const unsigned upv = L.up[r];  // (a value: the conditional below on the array element itself selects an address)
     hi[r] = __builtin_bit_cast(f16x2, odd ? upv : (second ? a : b));
   }
   const f16x2 wxy = __builtin_bit_cast(f16x2, L.wxy), wz = __builtin_bit_cast(f16x2, L.wzz);

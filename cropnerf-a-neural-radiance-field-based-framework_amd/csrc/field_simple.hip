@@ -255,8 +255,7 @@ constexpr size_t LDS_FLOATS = (size_t)3 * WMAX * LDA + ROWS_G * LDA + 64 * WS_MA
 // (Prefetching the next pass's weights into registers during the MFMAs was tried: no gain -- the cost of a pass is the
 // L2 -> LDS volume of re-staging 185 KB of weights per 64-sample tile, not its latency.)
 __device__ __forceinline__ void dense_mfma(const float* __restrict__ Wg, const float* __restrict__ bg_, int K_, int N_,
-                                           const float* in, float* out, bool relu, float* wbuf, int tid,
-                                           int debug_skip = 0) {
+                                           const float* in, float* out, bool relu, float* wbuf, int tid) {
   const float* __restrict__ bg = bg_;
   const int K = K_, N = N_;
   const int Kp = (K + 15) & ~15, ws = Kp + 4;
@@ -270,7 +269,7 @@ __device__ __forceinline__ void dense_mfma(const float* __restrict__ Wg, const f
       for (int k = lane; k < Kp; k += 64)
         wbuf[row * ws + k] = (row < rows && k < K) ? Wg[(size_t)(p0 + row) * K + k] : 0.f;
     __syncthreads();
-    for (int nt = nt0; nt < rows_p / 16 && !(debug_skip & 32); nt += 2) {
+    for (int nt = nt0; nt < rows_p / 16; nt += 2) {
       f32x4 acc;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -316,7 +315,7 @@ field_eval_mfma_kernel(FieldDev fp, SceneDev sc, int app_mode, int sh_unit, cons
                        const float* __restrict__ directions, const int64_t* __restrict__ cam_idx,
                        const float* __restrict__ starts, const float* __restrict__ ends, long long num_rays, int S,
                        float* __restrict__ density, float* __restrict__ rgb, float* __restrict__ semantics,
-                       float* __restrict__ positions, int debug_skip) {
+                       float* __restrict__ positions) {
   extern __shared__ __align__(16) float lds[];
   float* bufA = lds;
   float* bufB = bufA + WMAX * LDA;
@@ -353,7 +352,7 @@ field_eval_mfma_kernel(FieldDev fp, SceneDev sc, int app_mode, int sh_unit, cons
     }
     const bool sel = normalize_position(sc, px, py, pz);
     __syncthreads();  // the previous tile's readers of bufA / bufC are done
-    for (int l = grp; l < fp.grid.num_levels && !(debug_skip & 64); l += NW) {
+    for (int l = grp; l < fp.grid.num_levels; l += NW) {
       const float2 f = hash_level_any(fp.grid, l, px, py, pz);
       bufA[(2 * l) * LDA + s] = f.x;
       bufA[(2 * l + 1) * LDA + s] = f.y;
@@ -384,7 +383,7 @@ field_eval_mfma_kernel(FieldDev fp, SceneDev sc, int app_mode, int sh_unit, cons
       for (int l = 0; l < fp.base.num_layers; ++l) {
         const bool last = l == fp.base.num_layers - 1;
         float* y = last ? bufG : (x == bufA ? bufB : bufA);
-        dense_mfma(fp.base.w[l], fp.base.b[l], fp.base.dims[l], fp.base.dims[l + 1], x, y, !last, wbuf, tid, debug_skip);
+        dense_mfma(fp.base.w[l], fp.base.b[l], fp.base.dims[l], fp.base.dims[l + 1], x, y, !last, wbuf, tid);
         x = y;
       }
     }
@@ -397,8 +396,7 @@ field_eval_mfma_kernel(FieldDev fp, SceneDev sc, int app_mode, int sh_unit, cons
       const float* x = bufG + LDA;
       for (int l = 0; l < fp.sem.num_layers; ++l) {
         float* y = (x == bufA) ? bufB : bufA;
-        dense_mfma(fp.sem.w[l], fp.sem.b[l], fp.sem.dims[l], fp.sem.dims[l + 1], x, y, l < fp.sem.num_layers - 1, wbuf, tid,
-                   debug_skip);
+        dense_mfma(fp.sem.w[l], fp.sem.b[l], fp.sem.dims[l], fp.sem.dims[l + 1], x, y, l < fp.sem.num_layers - 1, wbuf, tid);
         x = y;
       }
       __syncthreads();
@@ -415,7 +413,7 @@ field_eval_mfma_kernel(FieldDev fp, SceneDev sc, int app_mode, int sh_unit, cons
       for (int l = 0; l < fp.color.num_layers; ++l) {
         float* y = (x == bufA) ? bufB : bufA;
         dense_mfma(fp.color.w[l], fp.color.b[l], fp.color.dims[l], fp.color.dims[l + 1], x, y,
-                   l < fp.color.num_layers - 1, wbuf, tid, debug_skip);
+                   l < fp.color.num_layers - 1, wbuf, tid);
         x = y;
       }
       __syncthreads();
@@ -569,10 +567,7 @@ extern "C" int cn_field_eval_mp(const cn_field_params* params, const cn_scene* s
     hipLaunchKernelGGL(cn::gm::field_eval_mfma_kernel, dim3(cn::grid_for(ntiles, 1, 256)), dim3(cn::gm::NT), lds_mfma,
                        cn::as_stream(stream), cn::make_field_dev(*params), cn::make_scene_dev(*scene), app_mode,
                        sh_unit_dir, origins, directions, camera_indices, starts, ends, (long long)num_rays, num_samples,
-                       density, rgb, semantics, positions, [] {
-                         const char* e = getenv("CN_DEBUG_SKIP");  // profiling aid: 32 no MFMA loops, 64 no gathers
-                         return e ? atoi(e) : 0;
-                       }());
+                       density, rgb, semantics, positions);
     return cn::check_launch("cn_field_eval");
   }
   long long nblk = (num_rays * (long long)num_samples + 63) / 64;

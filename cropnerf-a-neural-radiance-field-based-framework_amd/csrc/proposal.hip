@@ -18,7 +18,7 @@ namespace cn {
 // What bounds this kernel, and what was tried (round 3; C2 batch, eval):
 //  * x-pair gathers (hash_level_xpair: 40 gathers per evaluation become 30, 5.8e8 L1 line lookups per launch) bought 2 % while the
 //    MLP ran on the VALU (1.054 -> 1.030 ms) and LOSE now that it does not (0.678 vs 0.609 ms with plain hash_level): the selects and
-//    the branch of the pair form are VALU instructions, and VALU issue is what is left.  CN_PROP_XPAIR=1 builds it.
+//    the branch of the pair form are VALU instructions, and VALU issue is what is left.  Not kept.
 //  * the team form of the render kernels -- the four waves of a workgroup (four consecutive rays, neighbouring pixels) each
 //    evaluating 16 samples of a chunk for all four rays, rays in adjacent lanes, densities handed over through LDS; bit-identical
 //    results -- left the launch at 1.028 ms: the L1 lookups never bounded it.  Removed.
@@ -33,9 +33,6 @@ namespace cn {
 //    issue slots are taken.
 //  * ablation builds (-DCN_PROP_ABLATE=1 / 2), MLP on the VALU: 0.21 ms without any network, 0.58 ms with the hash encoding, 1.04 ms
 //    complete -- the MLP was the larger half; see prop_mlp_mfma.
-#ifndef CN_PROP_XPAIR
-#define CN_PROP_XPAIR 0
-#endif
 #ifndef CN_PROP_ABLATE
 #define CN_PROP_ABLATE 0
 #endif
@@ -75,7 +72,7 @@ struct PropArgs {
   float *final_starts, *final_ends;    // [R, s_final] (optional): euclidean_bins[:, :-1] / [:, 1:] as contiguous arrays
 };
 
-// The 2L -> 16 -> 1 MLP of a proposal network on the fp32 matrix cores (CN_PROP_MLP_MFMA, default).  On the VALU it was the
+// The 2L -> 16 -> 1 MLP of a proposal network on the fp32 matrix cores.  On the VALU it was the
 // larger half of the kernel (ablation builds, C2 batch: 0.21 ms without any network, 0.58 ms with the hash encoding, 1.04 ms
 // with the MLP: 176 multiply-adds per evaluation, whose 193 weights do not fit the scalar registers and were re-fetched with
 // scalar loads for every 64 evaluations).  Here the wave's 64 evaluations are four 16-column tiles of one product
@@ -210,9 +207,6 @@ __device__ __forceinline__ float prop_density_f16(const PropNet& n, const PropMl
   return expf(prop_mlp_f16<L>(mlp, encw, featp, lane)) * (sel ? 1.f : 0.f);
 }
 
-#ifndef CN_PROP_MLP_MFMA
-#define CN_PROP_MLP_MFMA 1
-#endif
 template <int L, int H, bool HALF>
 __device__ __forceinline__ float prop_density(const PropNet& n, const PropMlp& mlp, float* encT, int lane, const SceneDev& sc, float px,
                                               float py, float pz) {
@@ -225,11 +219,7 @@ __device__ __forceinline__ float prop_density(const PropNet& n, const PropMlp& m
   //  measured slower: 0.85 vs 0.67 ms per C2 launch, the second level in flight costs 20 registers and spills.)
 #pragma unroll
   for (int l = 0; l < L; ++l) {
-#if CN_PROP_XPAIR
-    float2 f = hash_level_xpair<HALF>(n.grid.table, n.grid.level(l), n.grid.pos_offset, px, py, pz);
-#else
     float2 f = hash_level<HALF>(n.grid.table, n.grid.level(l), n.grid.pos_offset, px, py, pz);
-#endif
     enc[2 * l] = f.x;
     enc[2 * l + 1] = f.y;
   }
@@ -241,19 +231,8 @@ __device__ __forceinline__ float prop_density(const PropNet& n, const PropMlp& m
     return expf(acc) * (sel ? 1.f : 0.f);
   }
 #endif
-#if CN_PROP_MLP_MFMA
   static_assert(H == 16, "one 16-row tile of hidden units");
   const float out = prop_mlp_mfma<L>(mlp, encT, enc, lane);
-#else
-  float out = n.b1[0];
-#pragma unroll
-  for (int h = 0; h < H; ++h) {
-    float a = n.b0[h];
-#pragma unroll
-    for (int k = 0; k < 2 * L; ++k) a = fmaf(n.w0[h * 2 * L + k], enc[k], a);
-    out = fmaf(n.w1[h], fmaxf(a, 0.f), out);
-  }
-#endif
   return expf(out) * (sel ? 1.f : 0.f);
 }
 

@@ -686,7 +686,7 @@ static size_t fused_workspace_bytes(const cn_field_params* p) {
 struct FusedDevice {
   int split_resident;  // workgroups of render_split_kernel the device holds at once (a multiple of 8 = XCD teams)
   int res_sample, res_density, res_full;  // resident blocks of the render_fused_kernel variants
-  int res_f16_sample, res_f16_density, res_f16_full;  // ... of the render_f16_kernel variants
+  int res_f16_density;  // ... of the density-only render_f16_kernel
 };
 
 template <typename K>
@@ -747,9 +747,7 @@ static hipError_t fused_device_init(int dev, FusedDevice& d) {
   CN_TRY(resident_blocks(render_fused_kernel<true, false, false, false>, cus, &d.res_sample));
   CN_TRY(resident_blocks(render_fused_kernel<false, true, false, false>, cus, &d.res_density));
   CN_TRY(resident_blocks(render_fused_kernel<false, false, false, false>, cus, &d.res_full));
-  CN_TRY(resident_blocks(render_f16_kernel<true, false, true, true>, cus, &d.res_f16_sample));
-  CN_TRY(resident_blocks(render_f16_kernel<false, true, true, true>, cus, &d.res_f16_density));
-  CN_TRY(resident_blocks(render_f16_kernel<false, false, true, true>, cus, &d.res_f16_full));
+  CN_TRY(resident_blocks(render_f16_kernel<true, true>, cus, &d.res_f16_density));
 #undef CN_TRY
   return hipSuccess;
 }
@@ -805,11 +803,9 @@ static int launch_fused(const cn_field_params* params, const cn_scene* scene, co
   // fp16 matrix mode: the composited and per-sample renders run the fp16 form of the producer/consumer kernel
   // (render_split_kernel<., MM_F16, ., .>) at EVERY batch size, so that a ray's result does not depend on the call it is part
   // of; the density-only pass, which the split kernel does not have, runs render_f16_kernel (render_f16.hpp).
-  // CN_F16_KERNEL=own is the A/B switch that sends all three through render_f16_kernel (2.9 vs 1.6 ms at C2).
   const bool want_f16 = opts->matrix_precision == CN_MATRIX_F16;
-  const char* f16_env = getenv("CN_F16_KERNEL");
-  const bool f16_split = want_f16 && !opts->density_only && !(f16_env && strcmp(f16_env, "own") == 0);
-  const bool f16_own = want_f16 && !f16_split;
+  const bool f16_density = want_f16 && opts->density_only && !PER_SAMPLE;
+  const bool f16_split = want_f16 && !f16_density;
   if (f16_split || (!want_f16 && !opts->density_only && split_mode && (PER_SAMPLE || early_stop == 0.f || split_mode > 1))) {
     const int resident = dev->split_resident;
     const long long work = PER_SAMPLE ? num_rays * ((opts->num_samples + 63) / 64) : num_rays;  // (ray, chunk) items
@@ -819,7 +815,7 @@ static int launch_fused(const cn_field_params* params, const cn_scene* scene, co
     if (want_s >= resident || split_mode > 1 || f16_split) split_blocks = (unsigned)(want_s < resident ? want_s : resident);
   }
   // split-bf16 matrix products: an option of the producer/consumer kernel only; elsewhere the products stay fp32
-  const int mm = (split_blocks > 0 || f16_own) ? opts->matrix_precision : CN_MATRIX_FP32;
+  const int mm = (split_blocks > 0 || f16_density) ? opts->matrix_precision : CN_MATRIX_FP32;
   const bool bf16 = mm == MM_BF16;
   A.grid = make_grid_dev(params->grid);
   const bool half = A.grid.half != 0;
@@ -881,14 +877,12 @@ static int launch_fused(const cn_field_params* params, const cn_scene* scene, co
   // ~400 rays are in flight per XCD; a stripe about 24 pixels wide makes that patch roughly square (measured at
   // 800 px: 1/2/4/8 stripes per XCD -> 3.57 / 3.78 / 3.83 / 3.66 Gsamples/s)
   A.stripes_per_xcd = A.image_width > 0 ? (A.image_width + 96) / 192 : 1;
-  if (const char* e = getenv("CN_STRIPES_PER_XCD")) A.stripes_per_xcd = atoi(e);  // tuning aid
   if (A.stripes_per_xcd < 1) A.stripes_per_xcd = 1;
   A.pixel_start = opts->pixel_start;
   // persistent grid: exactly the resident block count (a multiple of 8 = XCD groups), never more waves than rays
-  const long long cap = f16_own ? (PER_SAMPLE ? dev->res_f16_sample : (opts->density_only ? dev->res_f16_density : dev->res_f16_full))
-                                : (PER_SAMPLE ? dev->res_sample : (opts->density_only ? dev->res_density : dev->res_full));
-  const long long fused_items = (f16_own && PER_SAMPLE) ? num_rays * ((opts->num_samples + 63) / 64) : num_rays;
-  const long long want = (((fused_items + FUSED_WAVES - 1) / FUSED_WAVES) + 7) / 8 * 8;
+  const long long cap = f16_density ? dev->res_f16_density
+                                    : (PER_SAMPLE ? dev->res_sample : (opts->density_only ? dev->res_density : dev->res_full));
+  const long long want = (((num_rays + FUSED_WAVES - 1) / FUSED_WAVES) + 7) / 8 * 8;
   const unsigned blocks = (unsigned)(want < cap ? want : cap);
   if (split_blocks) {
     const size_t lds_bytes = bf16 ? SPLIT_LDS_BYTES_BF16 : SPLIT_LDS_BYTES;
@@ -925,22 +919,11 @@ static int launch_fused(const cn_field_params* params, const cn_scene* scene, co
 #undef CN_SPLIT_LAUNCH
     return check_launch(who);
   }
-  if (f16_own) {
-#define CN_F16_LAUNCH1(PS, DO, H)                                                                                  \
-  do {                                                                                                             \
-    if (generic) hipLaunchKernelGGL((render_f16_kernel<PS, DO, H, true>), dim3(blocks), dim3(FUSED_THREADS), 0, s, A);   \
-    else hipLaunchKernelGGL((render_f16_kernel<PS, DO, H, false>), dim3(blocks), dim3(FUSED_THREADS), 0, s, A);          \
-  } while (0)
-#define CN_F16_LAUNCH(PS, DO)              \
-  do {                                     \
-    if (half) CN_F16_LAUNCH1(PS, DO, true);  \
-    else CN_F16_LAUNCH1(PS, DO, false);      \
-  } while (0)
-    if (PER_SAMPLE) CN_F16_LAUNCH(true, false);
-    else if (opts->density_only) CN_F16_LAUNCH(false, true);
-    else CN_F16_LAUNCH(false, false);
-#undef CN_F16_LAUNCH
-#undef CN_F16_LAUNCH1
+  if (f16_density) {
+    if (half && generic) hipLaunchKernelGGL((render_f16_kernel<true, true>), dim3(blocks), dim3(FUSED_THREADS), 0, s, A);
+    else if (half) hipLaunchKernelGGL((render_f16_kernel<true, false>), dim3(blocks), dim3(FUSED_THREADS), 0, s, A);
+    else if (generic) hipLaunchKernelGGL((render_f16_kernel<false, true>), dim3(blocks), dim3(FUSED_THREADS), 0, s, A);
+    else hipLaunchKernelGGL((render_f16_kernel<false, false>), dim3(blocks), dim3(FUSED_THREADS), 0, s, A);
     return check_launch(who);
   }
 #define CN_FUSED_LAUNCH1(PS, DO, H)                                                                                \

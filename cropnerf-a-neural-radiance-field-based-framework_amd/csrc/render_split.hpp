@@ -57,16 +57,7 @@ namespace cn {
 // The team gather serves the fp16 and the split-bf16 matrix modes on either table type -- C2, ms per batch without / with
 // 4-ray teams: fp16 mode on the fp32 torch table 2.14 / 1.69, split-bf16 on it 1.81 / 1.71, split-bf16 on a tcnn fp16 table
 // 2.06 / 1.57 -- but NOT the exact-fp32 kernel, which is bound by SIMD issue, hides its gathers under the fp32 MFMAs and only
-// pays for the per-lane ray parameters: 2.59 / 2.78 (CN_TEAM_ALL=1 forces it there too, A/B).
-#ifndef CN_TEAM_XPAIR
-#define CN_TEAM_XPAIR 1
-#endif
-#ifndef CN_TEAM_ALL
-#define CN_TEAM_ALL 0
-#endif
-#ifndef CN_TEAM_ROW_WALK  // 1: the four rays of a team are four consecutive pixels of a row (A/B)
-#define CN_TEAM_ROW_WALK 0
-#endif
+// pays for the per-lane ray parameters: 2.59 / 2.78.
 #ifndef CN_SPLIT_G
 #define CN_SPLIT_G 8
 #endif
@@ -168,16 +159,11 @@ __device__ __forceinline__ void split_ray_setup(const FusedArgs& A, long long q,
     rr = xcd * per_xcd + q;
   }
   if (chunks_per_ray > 0) {  // work items are (ray, chunk) pairs
-#ifdef CN_PER_SAMPLE_RAY_MAJOR  // round-1 order: consecutive items = consecutive chunks of one ray
-    ray.chunk = (int)(rr % chunks_per_ray);
-    rr /= chunks_per_ray;
-#else
     // chunk-major: consecutive items -- the pairs of a workgroup, the adjacent lanes of a team gather -- are the SAME chunk
     // of consecutive rays (neighbouring points of the exporters' surface grid: they share grid cells), not chunks 64
     // samples apart on one ray
     ray.chunk = (int)(rr / A.num_rays);
     rr -= (long long)ray.chunk * A.num_rays;
-#endif
   }
   const long long r = __builtin_amdgcn_readfirstlane((int)rr);
   ray.r = r;
@@ -230,8 +216,8 @@ __global__ void __launch_bounds__(SPLIT_THREADS) render_split_kernel(FusedArgs A
   // rays (= pairs = gather waves) per team: 2 or 4 (1 = no team).  Per-sample outputs (the exporters' parallel rays, whose
   // neighbouring SAMPLES are as close as neighbouring rays) keep 16 consecutive samples of one ray per lane row: no team
   constexpr int TR = PER_SAMPLE ? CN_TEAM_RAYS_PS : CN_TEAM_RAYS;
-  constexpr bool TEAM = !PACK && (CN_TEAM_ALL || MM != MM_FP32) && TR > 1 && (SPLIT_MPG == 1) && (SPLIT_G % TR == 0) && !CN_ABLATE_GATHER;
-  constexpr bool QUAD = TEAM && TR == 4 && !CN_TEAM_ROW_WALK;  // stripes walked in 2 x 2 pixel blocks (split_ray_setup)
+  constexpr bool TEAM = !PACK && MM != MM_FP32 && TR > 1 && (SPLIT_MPG == 1) && (SPLIT_G % TR == 0) && !CN_ABLATE_GATHER;
+  constexpr bool QUAD = TEAM && TR == 4;  // stripes walked in 2 x 2 pixel blocks (split_ray_setup)
   extern __shared__ __align__(16) float lds[];
   constexpr int OFF_EXT = BLOB_FLOATS + SPLIT_PAIRS * PAIR_SCRATCH;  // BF16 only
   {
@@ -300,9 +286,6 @@ __global__ void __launch_bounds__(SPLIT_THREADS) render_split_kernel(FusedArgs A
   float my_dlogit = 0.f, my_sel = 0.f, my_sem = 0.f, my_r = 0.f, my_g = 0.f, my_b = 0.f;
   bool ray_stopped = false;  // matrix wave: this ray was terminated early (cn_render_opts.early_stop_transmittance)
 
-#ifdef CN_SPLIT_GATHER_PRIO  // A/B: gather waves win the VALU arbitration, so their loads are issued before the matrix waves' MLPs run
-  if (!matrix_role) __builtin_amdgcn_s_setprio(CN_SPLIT_GATHER_PRIO);
-#endif
   // One loop for both roles (same trip count, one workgroup barrier per half-step at its end).
   for (long long step = 0; step <= total; ++step) {
     if (!matrix_role) {
@@ -417,12 +400,9 @@ __global__ void __launch_bounds__(SPLIT_THREADS) render_split_kernel(FusedArgs A
                   const Lvl lv = lane_level_rec<GENERIC>(lds + OFF_LVL, A.grid, 4 * g + q, lvl_scale[q]);
 #pragma unroll
                   for (int h = 0; h < 2; ++h) {
-#if CN_TEAM_XPAIR  // aligned 16-byte (float table) / 8-byte (half table) pair gathers for the fp32 blend too: split-bf16 on the
+                    // aligned 16-byte (float table) / 8-byte (half table) pair gathers for the fp32 blend too: split-bf16 on the
                     // headline table 1.726 -> 1.686 ms (the fp16 blend of a half table has its own pair form above)
                     const float2 f = hash_level_xpair<HALF>(A.grid.table, lv, pos_off, px[h], py[h], pz[h]);
-#else
-                    const float2 f = hash_level_sc<HALF, GENERIC>(A.grid.table, lv, pos_off, px[h], py[h], pz[h]);
-#endif
                     if constexpr (F16) {
                       const f16x2 hp = {(_Float16)f.x, (_Float16)f.y};
                       featp[h][q] = __builtin_bit_cast(unsigned, hp);

@@ -397,8 +397,10 @@ __device__ __forceinline__ void hash_level_backward_cells_rows(float* __restrict
   }
 }
 
+#if CN_DETERMINISTIC_SCATTER
 // fold the cell-major levels into the gradient table and zero their touched records: one thread per (copy, cell) record,
-// all levels in one launch (workgroups [first_block[l], first_block[l + 1]) belong to level l)
+// all levels in one launch (workgroups [first_block[l], first_block[l + 1]) belong to level l).  Only the deterministic
+// build compiles it: the block form below sums in LDS with float atomics of four waves, in no fixed order.
 struct CellFoldArgs {
   CellScatter c;
   unsigned first_block[CN_CELL_LEVELS + 1];
@@ -449,9 +451,10 @@ __global__ void __launch_bounds__(256) cell_scatter_fold_kernel(CellFoldArgs F, 
     cn_atomic_add(gtab + 2 * (size_t)e + 1, v[2 * c + 1]);
   }
 }
-// The same fold by BLOCKS of 8 x 8 x 8 cells (round 4).  The kernel above adds every touched record's 16 values to the table
-// one float per atomic instruction: up to 16 requests per record and copy, 4.3e6 per call at 65 536 rays -- the fold was bound
-// by its own atomics (0.27 ms per call, three calls per iteration).  Here a workgroup owns a block of cells in up to four of
+#else
+// The product build's fold, by BLOCKS of 8 x 8 x 8 cells (round 4).  The per-record form adds every touched record's 16
+// values to the table one float per atomic instruction: up to 16 requests per record and copy, 4.3e6 per call at 65 536
+// rays -- the fold was bound by its own atomics (0.27 ms per call, three calls per iteration).  Here a workgroup owns a block of cells in up to four of
 // the level's copies, sums their records into the block's 9 x 9 x 9 vertices in LDS (ds_add_f32), and then adds every non-zero
 // vertex to the table ONCE, two lanes per vertex (its two features) and vertices in x order: the index function xors x into
 // the low bits, so the eight vertices of an aligned x-row of the block lie on one 64-byte line and travel as one request.
@@ -528,26 +531,10 @@ __global__ void __launch_bounds__(256) cell_scatter_fold_blocks_kernel(CellFoldB
     cn_atomic_add(gtab + 2 * (size_t)e + (i & 1), val);
   }
 }
+#endif
 inline void launch_cell_fold(const CellScatter& c, const GridDev& grid, float* gtab, hipStream_t stream) {
   if (!c.base || c.num_levels <= 0) return;
-  const char* form = getenv("CN_CELL_FOLD");  // "records": the first form, one thread per record (A/B runs; always in the
-  // deterministic test build: the block form sums in LDS with float atomics of four waves)
-  if (!CN_DETERMINISTIC_SCATTER && (!form || strcmp(form, "records") != 0)) {
-    CellFoldBlocksArgs B{};
-    B.c = c;
-    unsigned blocks = 0;
-    for (int l = 0; l < c.num_levels; ++l) {
-      B.first_block[l] = blocks;
-      B.lv[l] = grid.level(l);
-      B.nb[l] = (c.n[l] + 7) / 8;
-      B.groups[l] = (c.copies[l] + 3) / 4;
-      blocks += B.nb[l] * B.nb[l] * B.nb[l] * B.groups[l];
-    }
-    for (int l = c.num_levels; l <= CN_CELL_LEVELS; ++l) B.first_block[l] = blocks;
-    for (int l = c.num_levels; l < CN_CELL_LEVELS; ++l) B.nb[l] = B.groups[l] = 1;
-    hipLaunchKernelGGL(cell_scatter_fold_blocks_kernel, dim3(blocks), dim3(256), 0, stream, B, gtab);
-    return;
-  }
+#if CN_DETERMINISTIC_SCATTER
   CellFoldArgs F{};
   F.c = c;
   unsigned blocks = 0;
@@ -559,6 +546,21 @@ inline void launch_cell_fold(const CellScatter& c, const GridDev& grid, float* g
   }
   for (int l = c.num_levels; l <= CN_CELL_LEVELS; ++l) F.first_block[l] = blocks;
   hipLaunchKernelGGL(cell_scatter_fold_kernel, dim3(blocks), dim3(256), 0, stream, F, gtab);
+#else
+  CellFoldBlocksArgs B{};
+  B.c = c;
+  unsigned blocks = 0;
+  for (int l = 0; l < c.num_levels; ++l) {
+    B.first_block[l] = blocks;
+    B.lv[l] = grid.level(l);
+    B.nb[l] = (c.n[l] + 7) / 8;
+    B.groups[l] = (c.copies[l] + 3) / 4;
+    blocks += B.nb[l] * B.nb[l] * B.nb[l] * B.groups[l];
+  }
+  for (int l = c.num_levels; l <= CN_CELL_LEVELS; ++l) B.first_block[l] = blocks;
+  for (int l = c.num_levels; l < CN_CELL_LEVELS; ++l) B.nb[l] = B.groups[l] = 1;
+  hipLaunchKernelGGL(cell_scatter_fold_blocks_kernel, dim3(blocks), dim3(256), 0, stream, B, gtab);
+#endif
 }
 
 // fold the private copies into the gradient table and zero them again: 64 vertices of the dense n1^3 array per workgroup,
@@ -672,8 +674,6 @@ struct FieldBwdArgs {
   long long R;
   int S;
   float *d_pos, *d_dir;  // optional [R*S,3] outputs for the camera pose refinement (null: skipped)
-  int debug_skip;  // profiling aid (env CN_DEBUG_SKIP): 1 hash atomics, 2 embedding atomics, 4 weight-gradient dots,
-                   // 32 semantic branch, 64 forward gathers (matrix-core kernel), bits 8 + l: the scatter of level l
   CoarseScatter coarse;  // private copies for level 0's gradient (cn_grid.scatter_scratch of the gradient grid)
   CellScatter cells;     // cell-major records of the coarse levels (take precedence for the levels they cover)
 };
@@ -800,21 +800,21 @@ __global__ void __launch_bounds__(TB) field_backward_kernel(FieldBwdArgs A) {
       dA[wave * LD + lane] = up * s * (1.f - s);
     }
     __syncthreads();
-    if (!(A.debug_skip & 4)) gWc2.add(dA, c2, tid);
+    gWc2.add(dA, c2, tid);
     bias_add<3>(gbc2, dA, tid);
     bwd_rows<64, 3>(A.p.wc2, dA, dB, c2, 0, 64, wave, lane);  // delta_c2 (ReLU-gated) -> dB
     __syncthreads();
-    if (!(A.debug_skip & 4)) gWc1.add(dB, c1, tid);
+    gWc1.add(dB, c1, tid);
     bias_add<64>(gbc1, dB, tid);
     bwd_rows<64, 64>(A.p.wc1, dB, dA, c1, 0, 64, wave, lane);  // delta_c1 -> dA
     __syncthreads();
-    if (!(A.debug_skip & 4)) gWc0.add(dA, cin, tid);
+    gWc0.add(dA, cin, tid);
     bias_add<64>(gbc0, dA, tid);
     // delta of the colour input: geo rows (16..30) feed the base MLP, appearance rows (31..62) the embedding
     // (rows 0..15, the SH inputs, only when the direction gradient is wanted)
     bwd_rows<63, 64>(A.p.wc0, dA, dB, nullptr, A.d_dir ? 0 : 16, 63, wave, lane);  // dB rows 16..62
     __syncthreads();
-    if (A.app_per_camera && valid && !(A.debug_skip & 2)) {
+    if (A.app_per_camera && valid) {
       for (int k = wave; k < 32; k += 4) cn_atomic_add(A.g.emb + A.cam_idx[r] * 32 + k, dB[(31 + k) * LD + lane]);
     }
     if (A.d_dir && wave == 3 && valid) {
@@ -840,36 +840,34 @@ __global__ void __launch_bounds__(TB) field_backward_kernel(FieldBwdArgs A) {
     if (wave == 0) dA[lane] = misc[4 * LD + lane];
     for (int k = wave; k < 15; k += 4) dA[(1 + k) * LD + lane] = dB[(16 + k) * LD + lane];
     __syncthreads();
-    if (!(A.debug_skip & 4)) gW1.add(dA, h1, tid);
+    gW1.add(dA, h1, tid);
     bias_add<16>(gb1, dA, tid);
     bwd_rows<64, 16>(A.p.w1, dA, dB, h1, 0, 64, wave, lane);  // delta_h1 -> dB
     __syncthreads();
-    if (!(A.debug_skip & 4)) gW0.add(dB, enc, tid);
+    gW0.add(dB, enc, tid);
     bias_add<64>(gb0, dB, tid);
     bwd_rows<32, 64>(A.p.w0, dB, dA, nullptr, 0, 32, wave, lane);  // delta_enc -> dA rows 0..31
     __syncthreads();
-    if (!(A.debug_skip & 1)) {
-      const float px = misc[0 * LD + lane], py = misc[1 * LD + lane], pz = misc[2 * LD + lane];
-      float gpx = 0.f, gpy = 0.f, gpz = 0.f;
-      if (A.d_pos) {  // kernel-uniform
+    const float px = misc[0 * LD + lane], py = misc[1 * LD + lane], pz = misc[2 * LD + lane];
+    float gpx = 0.f, gpy = 0.f, gpz = 0.f;
+    if (A.d_pos) {  // kernel-uniform
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int l = 4 * wave + q;
-          hash_level_backward<true>(A.g.table, A.p.table, A.grid.level(l), A.grid.pos_offset, px, py, pz,
-                                    valid ? dA[(2 * l) * LD + lane] : 0.f, valid ? dA[(2 * l + 1) * LD + lane] : 0.f,
-                                    lane, gpx, gpy, gpz);
-        }
-        misc[(9 + 3 * wave) * LD + lane] = gpx;
-        misc[(10 + 3 * wave) * LD + lane] = gpy;
-        misc[(11 + 3 * wave) * LD + lane] = gpz;
-      } else {
+      for (int q = 0; q < 4; ++q) {
+        const int l = 4 * wave + q;
+        hash_level_backward<true>(A.g.table, A.p.table, A.grid.level(l), A.grid.pos_offset, px, py, pz,
+                                  valid ? dA[(2 * l) * LD + lane] : 0.f, valid ? dA[(2 * l + 1) * LD + lane] : 0.f,
+                                  lane, gpx, gpy, gpz);
+      }
+      misc[(9 + 3 * wave) * LD + lane] = gpx;
+      misc[(10 + 3 * wave) * LD + lane] = gpy;
+      misc[(11 + 3 * wave) * LD + lane] = gpz;
+    } else {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int l = 4 * wave + q;
-          hash_level_backward<false>(A.g.table, A.p.table, A.grid.level(l), A.grid.pos_offset, px, py, pz,
-                                     valid ? dA[(2 * l) * LD + lane] : 0.f, valid ? dA[(2 * l + 1) * LD + lane] : 0.f,
-                                     lane, gpx, gpy, gpz);
-        }
+      for (int q = 0; q < 4; ++q) {
+        const int l = 4 * wave + q;
+        hash_level_backward<false>(A.g.table, A.p.table, A.grid.level(l), A.grid.pos_offset, px, py, pz,
+                                   valid ? dA[(2 * l) * LD + lane] : 0.f, valid ? dA[(2 * l + 1) * LD + lane] : 0.f,
+                                   lane, gpx, gpy, gpz);
       }
     }
     __syncthreads();
@@ -889,15 +887,15 @@ __global__ void __launch_bounds__(TB) field_backward_kernel(FieldBwdArgs A) {
     }
     // ---- semantic branch: sem = Wh s2 + bh; gradients stop at the (detached) geo features ------------------------------
     // delta_sem (1 row) is misc row 5
-    if (!(A.debug_skip & 4)) gWh.add(misc + 5 * LD, s2, tid);
+    gWh.add(misc + 5 * LD, s2, tid);
     bias_add<1>(gbh, misc + 5 * LD, tid);
     bwd_rows<64, 1>(A.p.wh, misc + 5 * LD, dB, nullptr, 0, 64, wave, lane);  // delta_s2 -> dB
     __syncthreads();
-    if (!(A.debug_skip & 4)) gWs1.add(dB, s1, tid);
+    gWs1.add(dB, s1, tid);
     bias_add<64>(gbs1, dB, tid);
     bwd_rows<64, 64>(A.p.ws1, dB, dA, s1, 0, 64, wave, lane);  // delta_s1 -> dA
     __syncthreads();
-    if (!(A.debug_skip & 4)) gWs0.add(dA, o16 + LD, tid);
+    gWs0.add(dA, o16 + LD, tid);
     bias_add<64>(gbs0, dA, tid);
     __syncthreads();
   }
@@ -936,7 +934,6 @@ struct PropBwdArgs {
   float* d_pos;  // optional [R*S,3]
   long long R;
   int S;
-  int debug_skip;  // CN_DEBUG_SKIP: 8 hash atomics, 16 weight-gradient dots
   CoarseScatter coarse;
   CellScatter cells;  // cell-major records of the coarse levels (takes precedence over `coarse` for the levels it covers)
 };
@@ -1009,11 +1006,11 @@ __global__ void __launch_bounds__(TB, 4) proposal_backward_kernel(PropBwdArgs A)
       dout[lane] = up * misc[3 * LD + lane] * expf(fminf(fmaxf(logit, -15.f), 15.f));
     }
     __syncthreads();
-    if (!(A.debug_skip & 16)) gW1.add(dout, hid, tid);
+    gW1.add(dout, hid, tid);
     bias_add<1>(gb1, dout, tid);
     bwd_rows<H, 1>(A.w1, dout, dh, hid, 0, H, wave, lane);
     __syncthreads();
-    if (!(A.debug_skip & 16)) gW0.add(dh, enc, tid);
+    gW0.add(dh, enc, tid);
     bias_add<H>(gb0, dh, tid);
     // delta_enc[k] = sum_n W0[n][k] dh[n] -> straight into the table gradient
     float gpx = 0.f, gpy = 0.f, gpz = 0.f;
@@ -1030,7 +1027,6 @@ __global__ void __launch_bounds__(TB, 4) proposal_backward_kernel(PropBwdArgs A)
         g0 = fmaf(A.w0[n * K + 2 * l], d, g0);
         g1 = fmaf(A.w0[n * K + 2 * l + 1], d, g1);
       }
-      if ((A.debug_skip & 8) || ((A.debug_skip >> (8 + l)) & 1)) continue;  // bits 8..14: skip the scatter of level l (profiling)
       g0 = valid ? g0 : 0.f;
       g1 = valid ? g1 : 0.f;
       gpx += g0 * jx[round].x + g1 * jx[round].y;
@@ -1083,7 +1079,12 @@ __global__ void __launch_bounds__(TB, 4) proposal_backward_kernel(PropBwdArgs A)
 #include "train_proposal_wave.hpp"
 namespace cn {
 
-static double cell_scatter_ratio(bool proposal, double dflt);
+// cells-per-sample ratio up to which a level's gradient goes through cell-major records (see DESIGN 4.10 / 4.17):
+// CN_CELL_SCATTER sets it for every backward kernel (0 = off).
+static double cell_scatter_ratio(double dflt) {
+  const char* cs = getenv("CN_CELL_SCATTER");
+  return cs ? atof(cs) : dflt;
+}
 int validate_field(const cn_field_params& p);  // field_simple.hip
 int validate_grid(const cn_grid& g, const char* name);
 
@@ -1181,10 +1182,6 @@ extern "C" int cn_field_backward_ex(const cn_field_params* params, const cn_fiel
   A.d_dir = d_directions;
   A.R = num_rays;
   A.S = num_samples;
-  {
-    const char* dbg = getenv("CN_DEBUG_SKIP");
-    A.debug_skip = dbg ? atoi(dbg) : 0;
-  }
   // default: the matrix-core kernel; CN_FIELD_BACKWARD_IMPL=scalar selects the first (scalar-FMA) implementation,
   // kept as an independent device implementation for cross-checks
   const char* impl_env = getenv("CN_FIELD_BACKWARD_IMPL");  // read per call: one process can compare both
@@ -1220,7 +1217,7 @@ extern "C" int cn_field_backward_ex(const cn_field_params* params, const cn_fiel
     long long ntiles = (nsamp + cn::mf::TSM - 1) / cn::mf::TSM;
     A.coarse = cn::make_coarse_scatter(grads->grid);
     {  // cell-major records for the levels with at most CELL_RATIO_FIELD cells per sample (CN_CELL_SCATTER=<ratio>, 0: off)
-      const double ratio = cn::cell_scatter_ratio(false, cn::CELL_RATIO_FIELD);
+      const double ratio = cn::cell_scatter_ratio(cn::CELL_RATIO_FIELD);
       if (ratio != 0.0) A.cells = cn::make_cell_scatter(grads->grid, (unsigned long long)(nsamp * ratio), (unsigned long long)nsamp);
       if (A.cells.num_levels > 0) A.coarse.base = nullptr;  // level 0 is cell-major then
     }
@@ -1249,17 +1246,6 @@ extern "C" int cn_field_backward_ex(const cn_field_params* params, const cn_fiel
   CN_DET_FLUSH(cn::as_stream(stream));
   return CN_OK;
 }
-
-namespace cn {
-// cells-per-sample ratio up to which a level's gradient goes through cell-major records (see DESIGN 4.10 / 4.17):
-// CN_CELL_SCATTER sets it for every backward kernel (0 = off), CN_CELL_SCATTER_PROP for the proposal networks alone.
-static double cell_scatter_ratio(bool proposal, double dflt) {
-  const char* cs = getenv("CN_CELL_SCATTER");
-  const char* cp = proposal ? getenv("CN_CELL_SCATTER_PROP") : nullptr;
-  if (cp) return atof(cp);
-  return cs ? atof(cs) : dflt;
-}
-}  // namespace cn
 
 extern "C" int cn_proposal_backward(const cn_density_params* params, const cn_density_params* grads,
                                     const cn_scene* scene, const float* origins, const float* directions,
@@ -1299,15 +1285,11 @@ extern "C" int cn_proposal_backward(const cn_density_params* params, const cn_de
   A.d_pos = d_positions;
   A.R = num_rays;
   A.S = num_samples;
-  {
-    const char* dbg = getenv("CN_DEBUG_SKIP");
-    A.debug_skip = dbg ? atoi(dbg) : 0;
-  }
   A.coarse = cn::make_coarse_scatter(grads->grid);
   // cell-major records for the levels with at most CELL_RATIO_PROPOSAL cells per sample (runs of a ray's samples merge there);
-  // CN_CELL_SCATTER_PROP / CN_CELL_SCATTER = 0 keeps every level on the table path
+  // CN_CELL_SCATTER = 0 keeps every level on the table path
   {
-    const double ratio = cn::cell_scatter_ratio(true, cn::CELL_RATIO_PROPOSAL);
+    const double ratio = cn::cell_scatter_ratio(cn::CELL_RATIO_PROPOSAL);
     const unsigned long long nsamp = (unsigned long long)num_rays * (unsigned long long)num_samples;
     if (ratio != 0.0) A.cells = cn::make_cell_scatter(grads->grid, (unsigned long long)(nsamp * ratio), nsamp);
     if (A.cells.num_levels > 0 && A.coarse.base) A.coarse.base = nullptr;  // level 0 is cell-major then
@@ -1343,7 +1325,7 @@ extern "C" size_t cn_grid_scatter_scratch_bytes(const cn_grid* grid) {
 }
 
 // The same, sized for batches of at most `max_samples` samples per backward call: a level is kept cell-major only when it
-// has at most (CN_CELL_SCATTER / CN_CELL_SCATTER_PROP; defaults CELL_RATIO_FIELD / CELL_RATIO_PROPOSAL, at most
+// has at most (CN_CELL_SCATTER; defaults CELL_RATIO_FIELD / CELL_RATIO_PROPOSAL, at most
 // CELL_RATIO_MAX) x samples cells, so the records of levels with more than CELL_RATIO_MAX x max_samples cells would never be
 // touched.  max_samples <= 0: every level up to CELL_MAX_CELLS cells (= cn_grid_scatter_scratch_bytes).
 extern "C" size_t cn_grid_scatter_scratch_bytes_for(const cn_grid* grid, int64_t max_samples) {
@@ -1532,16 +1514,12 @@ extern "C" int cn_field_backward_general_ex(const cn_field_params* params, const
   const int grid = (int)std::min<long long>(ntiles, nblk);
   A.coarse = cn::make_coarse_scatter(grads->grid);
   {  // cell-major records (as in cn_field_backward) when the four LDS buffers that carry the hand-over hold two waves each
-    const double ratio = cn::cell_scatter_ratio(false, cn::CELL_RATIO_FIELD);
+    const double ratio = cn::cell_scatter_ratio(cn::CELL_RATIO_FIELD);
     const int small = std::min(std::min(p16(params->color.dims[1]), p16(params->color.dims[2])), p16(cin));
     if (ratio != 0.0 && small * cn::gb::LDG >= 2 * 64 * 17 && A.num_levels <= 16)
       A.cells = cn::make_cell_scatter(grads->grid, (unsigned long long)(num_rays * (double)num_samples * ratio),
                                       (unsigned long long)num_rays * (unsigned long long)num_samples);
     if (A.cells.num_levels > 0) A.coarse.base = nullptr;
-  }
-  {
-    const char* e = getenv("CN_DEBUG_SKIP");  // profiling aid (results are wrong by construction)
-    A.debug_skip = e ? atoi(e) : 0;
   }
   hipLaunchKernelGGL(cn::gb::field_backward_general_kernel, dim3(grid), dim3(cn::gb::NTG), lds, s, A);
   CN_DET_FLUSH(s);

@@ -359,9 +359,7 @@ __global__ void __launch_bounds__(NT) field_backward_mfma_kernel(FieldBwdArgs A)
     //  the position gradient of the tile is g0 * J.x + g1 * J.y at its end, no second gather -- hash_level_jac)
     v2f_t jx = {0.f, 0.f}, jy = {0.f, 0.f}, jz = {0.f, 0.f};
     if (live) {
-      // (bit 64, timing only: no table gathers in the forward recompute)
-      const float2 f = (A.debug_skip & 64) ? make_float2(px * 0.01f, py * 0.01f)
-                                           : hash_level_jac(A.p.table, my_lv, A.grid.pos_offset, px, py, pz, jx, jy, jz);
+      const float2 f = hash_level_jac(A.p.table, my_lv, A.grid.pos_offset, px, py, pz, jx, jy, jz);
       ENC[(2 * lvl) * LDA + s] = f.x;
       ENC[(2 * lvl + 1) * LDA + s] = f.y;
     }
@@ -403,7 +401,6 @@ __global__ void __launch_bounds__(NT) field_backward_mfma_kernel(FieldBwdArgs A)
     __syncthreads();
     __builtin_amdgcn_sched_barrier(0);
     if (have_prev) {  // the previous tile's hash-table gradient; its position gradient: the per-level partials are in A1
-    if (!(A.debug_skip & 1)) {
       float gpx = 0.f, gpy = 0.f, gpz = 0.f;  // (unused: the <false> forms do not touch them)
       // (a wave holds two levels, 32 lanes each: the branch below splits it along whole 16-lane rows, which is all the
       //  DPP run-length reduction and the quad rounds reach across)
@@ -423,25 +420,24 @@ __global__ void __launch_bounds__(NT) field_backward_mfma_kernel(FieldBwdArgs A)
       } else
         hash_level_backward<false>(A.g.table, A.p.table, my_lv, A.grid.pos_offset, p_px, p_py, p_pz, p_g0, p_g1, lane, gpx,
                                    gpy, gpz);
-    }
-    if (A.d_pos) {
-      // one thread per sample sums the 16 levels' partials, written at the end of the previous trip (A1 is not written before
-      // the s1 phase, two barriers away)
-      const float* part = A1;
-      if (lvl == 0 && p_valid) {
-        float gx = 0.f, gy = 0.f, gz = 0.f;
+      if (A.d_pos) {
+        // one thread per sample sums the 16 levels' partials, written at the end of the previous trip (A1 is not written before
+        // the s1 phase, two barriers away)
+        const float* part = A1;
+        if (lvl == 0 && p_valid) {
+          float gx = 0.f, gy = 0.f, gz = 0.f;
 #pragma unroll
-        for (int l = 0; l < 16; ++l) {
-          gx += part[(3 * l + 0) * LDA + s];
-          gy += part[(3 * l + 1) * LDA + s];
-          gz += part[(3 * l + 2) * LDA + s];
+          for (int l = 0; l < 16; ++l) {
+            gx += part[(3 * l + 0) * LDA + s];
+            gy += part[(3 * l + 1) * LDA + s];
+            gz += part[(3 * l + 2) * LDA + s];
+          }
+          normalize_position_backward(A.scene, p_wx, p_wy, p_wz, p_self, gx, gy, gz);
+          A.d_pos[3 * p_ismp] = gx;
+          A.d_pos[3 * p_ismp + 1] = gy;
+          A.d_pos[3 * p_ismp + 2] = gz;
         }
-        normalize_position_backward(A.scene, p_wx, p_wy, p_wz, p_self, gx, gy, gz);
-        A.d_pos[3 * p_ismp] = gx;
-        A.d_pos[3 * p_ismp + 1] = gy;
-        A.d_pos[3 * p_ismp + 2] = gz;
       }
-    }
     }
     if (!live) break;
     __builtin_amdgcn_sched_barrier(0);
@@ -464,7 +460,6 @@ __global__ void __launch_bounds__(NT) field_backward_mfma_kernel(FieldBwdArgs A)
     __syncthreads();
     __builtin_amdgcn_sched_barrier(0);
     // ---- semantic branch (its input is the DETACHED geo unless PSG: then d_geo += W_s0^T d_s1, see the c1 phase) --------
-    if (!(A.debug_skip & 32)) {  // (bit 32, timing only: the semantic branch's four phases skipped)
     store_blk<true>(A1, n0, s0, blk_fwd<16, MM>(Ws0, 20, n0, O16 + LDA, s0, bias4(lds + B_S0, n0, lane), lane), lane);
     __syncthreads();
     __builtin_amdgcn_sched_barrier(0);
@@ -485,7 +480,6 @@ __global__ void __launch_bounds__(NT) field_backward_mfma_kernel(FieldBwdArgs A)
     }
     __syncthreads();
     __builtin_amdgcn_sched_barrier(0);
-    }
     // ---- colour branch -----------------------------------------------------------------------------------------------------
     if (wave < 4) gX = blk_dw<MM>(D1, 16 * wave, O16 + LDA, 0, gX, lane);                               // dW sem0
     if (PSG && (wave == 4 || wave == 5)) {  // d_geo of the semantic MLP: geo input j -> DO16 row j + 1 (free until d_o16)
@@ -562,7 +556,7 @@ __global__ void __launch_bounds__(NT) field_backward_mfma_kernel(FieldBwdArgs A)
       // consecutive ones (one camera row each): sum the runs of equal ray inside every 16-lane row first and let the last
       // lane of a run add the two sums -- per-sample atomics on a straddling tile were 1024 same-address requests per tile
       // (3.1 of the kernel's 19.2 ms at 65 536 rays x 48 samples, where every third tile straddles two rays).
-      if (A.app_per_camera && !(A.debug_skip & 2)) {
+      if (A.app_per_camera) {
         float g0 = valid ? DCIN[(31 + 2 * lvl) * LDA + s] : 0.f;
         float g1 = valid ? DCIN[(32 + 2 * lvl) * LDA + s] : 0.f;
         const bool last = row_run_reduce(valid ? (unsigned)r : 0xffffffffu, g0, g1, lane & 15);
@@ -606,14 +600,12 @@ __global__ void __launch_bounds__(NT) field_backward_mfma_kernel(FieldBwdArgs A)
     __builtin_amdgcn_sched_barrier(0);
     gB0 = blk_dw<MM>(D2, 16 * (wave >> 1), ENC, 16 * (wave & 1), gB0, lane);                            // dW base0
     {
-      const bool lvl_off = (A.debug_skip >> (8 + lvl)) & 1;  // bits 8..23: skip the scatter of level l (profiling)
-      p_g0 = valid && !lvl_off ? D1[(2 * lvl) * LDA + s] : 0.f;
-      p_g1 = valid && !lvl_off ? D1[(2 * lvl + 1) * LDA + s] : 0.f;
+      p_g0 = valid ? D1[(2 * lvl) * LDA + s] : 0.f;
+      p_g1 = valid ? D1[(2 * lvl + 1) * LDA + s] : 0.f;
       if (A.d_pos) {  // this (sample, level)'s share of d(loss)/d(normalised position); A1 is dead since the d_c1 phase
-        const bool pos_off = (A.debug_skip & 1) != 0;
-        A1[(3 * lvl + 0) * LDA + s] = pos_off ? 0.f : p_g0 * jx.x + p_g1 * jx.y;
-        A1[(3 * lvl + 1) * LDA + s] = pos_off ? 0.f : p_g0 * jy.x + p_g1 * jy.y;
-        A1[(3 * lvl + 2) * LDA + s] = pos_off ? 0.f : p_g0 * jz.x + p_g1 * jz.y;
+        A1[(3 * lvl + 0) * LDA + s] = p_g0 * jx.x + p_g1 * jx.y;
+        A1[(3 * lvl + 1) * LDA + s] = p_g0 * jy.x + p_g1 * jy.y;
+        A1[(3 * lvl + 2) * LDA + s] = p_g0 * jz.x + p_g1 * jz.y;
       }
       p_px = px;
       p_py = py;
@@ -632,24 +624,22 @@ __global__ void __launch_bounds__(NT) field_backward_mfma_kernel(FieldBwdArgs A)
   __syncthreads();
 
   // ---- flush -------------------------------------------------------------------------------------------------------------
-  if (!(A.debug_skip & 4)) {
-    __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      const int blk = 2 * wave + b;
-      __builtin_amdgcn_sched_barrier(0);
-      flush_dw(A.g.ws1, 64, 64, 16 * (blk >> 2), 16 * (blk & 3), gS1[b], lane);
-      flush_dw(A.g.wc1, 64, 64, 16 * (blk >> 2), 16 * (blk & 3), gC1[b], lane);
-      flush_dw(A.g.wc0, 64, 63, 16 * (blk >> 2), 16 * (blk & 3), gC0[b], lane);
-    }
-    flush_dw(A.g.w0, 64, 32, 16 * (wave >> 1), 16 * (wave & 1), gB0, lane);
-    if (wave < 4) {
-      flush_dw(A.g.ws0, 64, 15, 16 * wave, 0, gX, lane);
-      flush_dw(A.g.wc2, 3, 64, 0, 16 * wave, gY, lane);
-    } else {
-      flush_dw(A.g.w1, 16, 64, 0, 16 * (wave - 4), gX, lane);
-      flush_dw(A.g.wh, 1, 64, 0, 16 * (wave - 4), gY, lane);
-    }
+  for (int b = 0; b < 2; ++b) {
+    const int blk = 2 * wave + b;
+    __builtin_amdgcn_sched_barrier(0);
+    flush_dw(A.g.ws1, 64, 64, 16 * (blk >> 2), 16 * (blk & 3), gS1[b], lane);
+    flush_dw(A.g.wc1, 64, 64, 16 * (blk >> 2), 16 * (blk & 3), gC1[b], lane);
+    flush_dw(A.g.wc0, 64, 63, 16 * (blk >> 2), 16 * (blk & 3), gC0[b], lane);
+  }
+  flush_dw(A.g.w0, 64, 32, 16 * (wave >> 1), 16 * (wave & 1), gB0, lane);
+  if (wave < 4) {
+    flush_dw(A.g.ws0, 64, 15, 16 * wave, 0, gX, lane);
+    flush_dw(A.g.wc2, 3, 64, 0, 16 * wave, gY, lane);
+  } else {
+    flush_dw(A.g.w1, 16, 64, 0, 16 * (wave - 4), gX, lane);
+    flush_dw(A.g.wh, 1, 64, 0, 16 * (wave - 4), gY, lane);
   }
   flush_bias(A.g.bs1, n0, bS1, lane);
   flush_bias(A.g.bs0, n0, bS0, lane);

@@ -187,16 +187,14 @@ __global__ void __launch_bounds__(256, 4) proposal_backward_wave_kernel(PropBwdA
     for (int k = 0; k < K; ++k) xenc[k * XS + lane] = enc[k];
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    if (!(A.debug_skip & 16)) {
 #pragma unroll
-      for (int sb = 0; sb < 4; ++sb) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(xdh + i16 * XS + 16 * sb + 4 * q);
-        const f32x4 b = *reinterpret_cast<const f32x4*>(xenc + i16 * XS + 16 * sb + 4 * q);
+    for (int sb = 0; sb < 4; ++sb) {
+      const f32x4 a = *reinterpret_cast<const f32x4*>(xdh + i16 * XS + 16 * sb + 4 * q);
+      const f32x4 b = *reinterpret_cast<const f32x4*>(xenc + i16 * XS + 16 * sb + 4 * q);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float av = a[e], bv = b[e];
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
-        }
+      for (int e = 0; e < 4; ++e) {
+        const float av = a[e], bv = b[e];
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
       }
     }
     __builtin_amdgcn_wave_barrier();
@@ -206,7 +204,6 @@ __global__ void __launch_bounds__(256, 4) proposal_backward_wave_kernel(PropBwdA
     asm volatile("" : "+v"(px), "+v"(py), "+v"(pz));
 #pragma unroll
     for (int l = L - 1; l >= 0; --l) {
-      if ((A.debug_skip & 8) || ((A.debug_skip >> (8 + l)) & 1)) continue;  // profiling: skip the scatter (of level l)
       const float g0 = denc[2 * l], g1 = denc[2 * l + 1];
       float ux = 0.f, uy = 0.f, uz = 0.f;  // (unused: the <false> forms do not touch them)
       if (l < A.cells.num_levels) {

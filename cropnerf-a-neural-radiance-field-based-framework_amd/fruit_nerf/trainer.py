@@ -91,14 +91,6 @@ class FruitTrainer:
         # nerfstudio's distance-squared gradient scaling (fruit_nerf.py:553-554): flags of the backward kernels, fixed from here on
         self.train_flags = ((L.TRAIN_PASS_SEMANTIC_GRADIENTS if model.config.pass_semantic_gradients else 0)
                             | (L.TRAIN_GRADIENT_SCALING if model.config.use_gradient_scaling else 0))
-        # the proposal sampler of the training forward as ONE launch (cn_proposal_sample_train) when the proposal networks
-        # have the shapes it is built for; CN_TRAIN_FUSED_SAMPLER=0 composes the materialising calls instead (A/B, tests)
-        self.fused_sampler = os.environ.get("CN_TRAIN_FUSED_SAMPLER", "1") != "0"
-        # CN_TRAIN_CONCURRENT_BACKWARD=1: field / proposal backward passes on three streams (forward_backward).  Off by default:
-        # measured 39.7 vs 40.4 ms at 65 536 rays and 3.06 vs 3.04 ms at 4 096 -- the field backward's workgroup owns a CU's whole
-        # LDS, so the kernels share the device CU by CU instead of overlapping on a CU
-        self.concurrent_backward = os.environ.get("CN_TRAIN_CONCURRENT_BACKWARD", "0") != "0" and model.device.type == "cuda"
-        self._side_streams = [torch.cuda.Stream(device=model.device) for _ in range(2)] if self.concurrent_backward else []
         self.groups = groups or {"proposal_networks": OptimGroup(), "fields": OptimGroup(),
                                  "camera_opt": OptimGroup(1e-3, 1e-15, 1e-4, 5000)}
         self._general_ws = None
@@ -250,8 +242,8 @@ class FruitTrainer:
         scene = m._scene(True)
         # ---- proposal sampler (bins, intervals and densities of every level are kept for the interlevel loss) --------
         s_prop = [int(v) for v in cfg.num_proposal_samples_per_ray[:n_lvl]]
-        if self.fused_sampler and ops.proposal_sample_fused_supported(m.proposal_networks, s_prop, cfg.num_nerf_samples_per_ray):
-            # one launch: cn_proposal_sample_train
+        if ops.proposal_sample_fused_supported(m.proposal_networks, s_prop, cfg.num_nerf_samples_per_ray):
+            # one launch (cn_proposal_sample_train) when the proposal networks have the shapes it is built for
             ps = ops.proposal_sample_train(m.proposal_networks, scene, o, d, nears, fars, s_prop,
                                            cfg.num_nerf_samples_per_ray, m._anneal if anneal_dev is None else anneal_dev,
                                            jitter_rows if jitter_rows is not None else
@@ -289,9 +281,7 @@ class FruitTrainer:
         #  sum over rays goes to loss_sums[4], the epilogue divides)
         rb_out = ops.train_render_backward(starts, ends, fo["density"], fo["rgb"], fo["semantics"], image, mask,
                                            cfg.semantic_loss_weight, self.loss_sums, spacing_bins=bins, flags=self.train_flags)
-        # The three backward passes (field, proposal network 0, proposal network 1) only share read-only inputs, so they run
-        # on three streams when self.concurrent_backward: each is bound by the float-atomic request rate of its scatter for
-        # part of its time and by matrix / gather work for the rest, and the parts of different kernels overlap on a CU.
+        # (the three backward passes run in order on one stream: on three streams they were measured no faster)
         def field_pass(d_o_acc, d_d_acc):
             dpos = torch.empty(R, S, 3, device=dev) if self.train_pose else None
             ddir = torch.empty(R, S, 3, device=dev) if self.train_pose else None
@@ -323,39 +313,15 @@ class FruitTrainer:
             if self.train_pose:
                 ops.ray_backward(dpos, None, lv["starts"], lv["ends"], d_o_acc, d_d_acc)
 
-        if self.concurrent_backward and len(levels) <= len(self._side_streams):
-            main = torch.cuda.current_stream()
-            fork = torch.cuda.Event()
-            fork.record(main)
-            partial = []
-            for lvl in range(len(levels)):
-                side = self._side_streams[lvl]
-                side.wait_event(fork)
-                with torch.cuda.stream(side):
-                    acc = (torch.zeros(R, 3, device=dev), torch.zeros(R, 3, device=dev)) if self.train_pose else (None, None)
-                    proposal_pass(lvl, *acc)
-                    done = torch.cuda.Event()
-                    done.record(side)
-                    partial.append((acc, done))
-            field_pass(d_o if self.train_pose else None, d_d if self.train_pose else None)
-            for acc, done in partial:
-                main.wait_event(done)
-                if self.train_pose:
-                    d_o += acc[0]
-                    d_d += acc[1]
-            ready("fields")
-            if update_proposals:
-                ready("proposal_networks")
-        else:
-            if 1 <= len(levels) <= 4:
-                dd_levels = ops.interlevel_backward_levels(bins, rb_out["weights"], levels, cfg.interlevel_loss_mult,
-                                                           self.loss_sums[2:3])
-            field_pass(d_o if self.train_pose else None, d_d if self.train_pose else None)
-            ready("fields")
-            for lvl in range(len(levels)):
-                proposal_pass(lvl, d_o if self.train_pose else None, d_d if self.train_pose else None)
-            if update_proposals:
-                ready("proposal_networks")
+        if 1 <= len(levels) <= 4:
+            dd_levels = ops.interlevel_backward_levels(bins, rb_out["weights"], levels, cfg.interlevel_loss_mult,
+                                                       self.loss_sums[2:3])
+        field_pass(d_o if self.train_pose else None, d_d if self.train_pose else None)
+        ready("fields")
+        for lvl in range(len(levels)):
+            proposal_pass(lvl, d_o if self.train_pose else None, d_d if self.train_pose else None)
+        if update_proposals:
+            ready("proposal_networks")
         if self.train_pose:
             gp = self.grads["camera_optimizer.pose_adjustment"]
             ops.pose_adjustment_backward(pose, cam, d_raw, d_o, d_d, gp)
@@ -498,9 +464,9 @@ class FruitTrainer:
         n_lvl = len(m.proposal_networks)
         # the captured iteration reads the annealing exponent from device memory, which only the one-launch sampler does: the
         # materialising sampler calls take it as a host float that a capture would freeze at its value of iteration ~2
-        fused = self.fused_sampler and ops.proposal_sample_fused_supported(
+        fused = ops.proposal_sample_fused_supported(
             m.proposal_networks, [int(v) for v in cfg.num_proposal_samples_per_ray[:n_lvl]], cfg.num_nerf_samples_per_ray)
-        return (fused and self.use_graph and not self.general and not self.concurrent_backward and self.model.device.type == "cuda"
+        return (fused and self.use_graph and not self.general and self.model.device.type == "cuda"
                 and all(g.optimizer == "adam" for g in self.groups.values())
                 and not (dist.is_available() and dist.is_initialized() and (dist.get_world_size() > 1 or self.force_exchange)))
 
@@ -654,17 +620,12 @@ class FruitTrainer:
         exchange = None
         if dist.is_available() and dist.is_initialized() and (dist.get_world_size() > 1 or self.force_exchange):
             # data-parallel training: each group's gradients are averaged under the kernels that follow their last writer
-            # (CN_DP_EXCHANGE=blocking: one all-reduce of the whole buffer after the backward, the round-3 form, for A/B runs)
-            if os.environ.get("CN_DP_EXCHANGE", "overlap") == "blocking":
-                out = self.forward_backward(ray_bundle, batch, update_proposals=updated)
-                self.all_reduce_gradients()
-            else:
-                exchange = self.gradient_exchange(force=self.force_exchange)
-                exchange.begin_iteration()
-                # (only the groups this iteration steps: a frozen group's gradients are zeroed, not averaged -- an exchange
-                #  nobody waits for would race with that fill)
-                out = self.forward_backward(ray_bundle, batch, update_proposals=updated, on_group_ready=lambda g: (
-                    exchange.start(g) if self._group_stepped(g, updated) else None))
+            exchange = self.gradient_exchange(force=self.force_exchange)
+            exchange.begin_iteration()
+            # (only the groups this iteration steps: a frozen group's gradients are zeroed, not averaged -- an exchange
+            #  nobody waits for would race with that fill)
+            out = self.forward_backward(ray_bundle, batch, update_proposals=updated, on_group_ready=lambda g: (
+                exchange.start(g) if self._group_stepped(g, updated) else None))
         else:
             out = self.forward_backward(ray_bundle, batch, update_proposals=updated)
         if updated:

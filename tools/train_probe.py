@@ -1,6 +1,6 @@
-"""Times the default fruit_nerf training iteration (TRAIN_RAYS random rays, default 4096) on cuda:0; CN_DEBUG_SKIP ablates parts of
-cn_field_backward (1 hash atomics, 2 embedding atomics, 4 weight-gradient dots).  TRAIN_PASS_SEM=1 / TRAIN_GRAD_SCALING=1 turn
-on pass_semantic_gradients / use_gradient_scaling (their cost against the default iteration).  Profiling aid, not a test."""
+"""Times the default fruit_nerf training iteration (TRAIN_RAYS random rays, default 4096) on cuda:0.  TRAIN_PASS_SEM=1 /
+TRAIN_GRAD_SCALING=1 turn on pass_semantic_gradients / use_gradient_scaling (their cost against the default iteration).
+Profiling aid, not a test."""
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cropnerf_amd import config as PC, ops, synthetic
@@ -41,4 +41,4 @@ if os.environ.get("PER_ITER") == "1":  # one line per iteration, each waited for
 for i in range(WARM): tr.train_iteration(rb, batch)
 torch.cuda.synchronize(); t=time.perf_counter()
 for i in range(ITERS): tr.train_iteration(rb, batch)
-torch.cuda.synchronize(); print("CN_DEBUG_SKIP", os.environ.get("CN_DEBUG_SKIP"), "flags", tr.train_flags, "rays", R, "ms/iter", (time.perf_counter()-t)/ITERS*1e3)
+torch.cuda.synchronize(); print("flags", tr.train_flags, "rays", R, "ms/iter", (time.perf_counter()-t)/ITERS*1e3)
