@@ -123,30 +123,71 @@ struct SplitRay {
   bool valid;
 };
 
-// ray of schedule slot q for this pair (same mapping as render_fused_kernel).  QUAD: a column stripe is walked in 2 x 2
-// pixel blocks -- four consecutive slots are one block, (x, y), (x + 1, y), (x, y + 1), (x + 1, y + 1) -- instead of pixel by
-// pixel along its rows: the four-ray team gather puts a block into a lane quad.
+// Slot -> ray schedule of an XCD team (the workgroups b, b + 8, ... share an XCD, hence an L2).
+//   * no image hint, or per-sample outputs: each XCD takes one contiguous eighth of the work items (per_xcd);
+//   * image hint, one ray per gather wave (the walk of render_fused_kernel): the XCD sweeps its column stripes x, x + 8, ...
+//     top to bottom, row by row over every image row the batch touches (rows, cw, first_row; slots outside the batch are
+//     idle steps);
+//   * image hint, four-ray teams (QUAD, QuadSched below): only the batch's pixels, every XCD and pair an equal share.
+// QuadSched: the pixels of the batch in two regions.  The BLOCK region is the batch's full rows taken in pairs (nb bands)
+// over the columns [0, wq), wq = the width rounded down to even, cut into column stripes cw (even) pixels wide -- the last
+// one narrower -- and each stripe walked band by band in 2 x 2 pixel blocks: four consecutive slots are one block, (x, y),
+// (x + 1, y), (x, y + 1), (x + 1, y + 1) -- the four-ray team gather puts a block into a lane quad.  The REST is what the
+// blocks leave, in pixel order: the partial first row (nh pixels), the last column of the band rows when the width is odd
+// (nodd), and from ray t0 on an odd last full row and the partial last row.  Each region is cut into 8 contiguous,
+// near-equal ranges (block ranges a multiple of 4, so that a team's four slots stay one block) and XCD x takes its range
+// of each: block slots [qlo, qlo + nq) first, then rest slots from llo.  Every slot is a ray, and an XCD holds ceil(rays / 8)
+// slots up to that rounding: 8 192 of a 65 536-ray batch, 32 per pair on 256 workgroups.
+struct QuadSched {
+  int cw, wq, span, ns1, nh, nodd, t0, qlo, nq, llo;  // span = pixels of a full-width stripe, ns1 = index of the last stripe
+};
+
+// the schedule slots of XCD `xcd` (rays of batch [pixel_start, pixel_start + num_rays) of an image_width-wide image)
+__device__ __forceinline__ long long quad_sched_init(const FusedArgs& A, int xcd, QuadSched& P) {
+  const int W = A.image_width, nstripe = 8 * A.stripes_per_xcd, R = (int)A.num_rays;
+  const long long p0 = A.pixel_start, p1 = p0 + A.num_rays;
+  const long long fr0 = (p0 + W - 1) / W;  // first full row
+  const int nb = (int)(max(p1 / W - fr0, 0LL) >> 1);
+  P.cw = 2 * ((W + 2 * nstripe - 1) / (2 * nstripe));
+  P.wq = W & ~1;
+  P.span = 2 * nb * P.cw;
+  P.ns1 = P.wq > 0 ? (P.wq - 1) / P.cw : 0;
+  P.nh = (int)(min(fr0 * W, p1) - p0);
+  P.nodd = 2 * nb * (W - P.wq);
+  P.t0 = P.nh + 2 * nb * W;
+  const int nblk = 2 * nb * P.wq, nrest = R - nblk;
+  const int pq = (((nblk + 7) >> 3) + 3) & ~3, pl = (nrest + 7) >> 3;
+  P.qlo = min(xcd * pq, nblk);
+  P.nq = min(pq, nblk - P.qlo);
+  P.llo = min(xcd * pl, nrest);
+  return P.nq + min(pl, nrest - P.llo);
+}
+
+// ray of schedule slot q for this pair
 template <bool QUAD = false>
 __device__ __forceinline__ void split_ray_setup(const FusedArgs& A, long long q, long long items, int xcd, bool striped,
                                                 long long rows, int cw, long long first_row, long long per_xcd,
-                                                int chunks_per_ray, SplitRay& ray) {
+                                                const QuadSched& P, int chunks_per_ray, SplitRay& ray) {
   ray.valid = false;
   ray.chunk = 0;
   if (q >= items) return;
   long long rr;
   if (striped) {
     if constexpr (QUAD) {
-    const int cwb = (cw + 1) >> 1;
-    const long long per_stripe = ((rows + 1) >> 1) * cwb * 4;
-    const long long sq = q / per_stripe;
-    const long long qq = q - sq * per_stripe;
-    const long long b = qq >> 2;
-    const int w = (int)(qq & 3);
-    const long long vrow = 2 * (b / cwb) + (w >> 1);
-    const int cx = 2 * (int)(b % cwb) + (w & 1);
-    const int col = (int)(sq * 8 + xcd) * cw + cx;
-    rr = (first_row + vrow) * A.image_width + col - A.pixel_start;
-    if (cx >= cw || vrow >= rows || col >= A.image_width || rr < 0 || rr >= A.num_rays) return;
+      const int W = A.image_width;
+      if (q < P.nq) {
+        const unsigned e = (unsigned)(P.qlo + (int)q);
+        const int s = min((int)(e / (unsigned)P.span), P.ns1);
+        const unsigned l = e - (unsigned)(s * P.span);
+        const int ws = min(P.cw, P.wq - s * P.cw);  // the last stripe may be narrower
+        const unsigned band = l / (unsigned)(2 * ws);
+        const int t = (int)(l - band * (unsigned)(2 * ws));
+        const int col = s * P.cw + 2 * (t >> 2) + (t & 1);
+        rr = P.nh + (int)(2 * band + ((t >> 1) & 1)) * W + col;
+      } else {
+        const int l = P.llo + (int)(q - P.nq);
+        rr = l < P.nh ? l : (l < P.nh + P.nodd ? P.nh + (l - P.nh) * W + W - 1 : P.t0 + (l - P.nh - P.nodd));
+      }
     } else {
     const long long sq = q / (rows * cw);
     const long long qq = q - sq * rows * cw;
@@ -261,12 +302,12 @@ __global__ void __launch_bounds__(SPLIT_THREADS) render_split_kernel(FusedArgs A
   const long long first_row = striped ? A.pixel_start / A.image_width : 0;
   const long long last_row = striped ? (A.pixel_start + A.num_rays - 1) / A.image_width : 0;
   const long long rows = last_row - first_row + 1;
-  const long long items =
-      !striped ? min(per_xcd, max(nwork - xcd * per_xcd, 0LL))
-               : (QUAD ? ((rows + 1) >> 1) * ((cw + 1) >> 1) * 4 : rows * cw) * A.stripes_per_xcd;
+  QuadSched qs;
+  const long long items = !striped ? min(per_xcd, max(nwork - xcd * per_xcd, 0LL))
+                                   : (QUAD ? quad_sched_init(A, xcd, qs) : rows * cw * A.stripes_per_xcd);
 
   // every wave of the workgroup runs the same number of half-steps (the barrier count must match): the schedule slots
-  // of pair 0, the longest list; a slot without a ray (past the end, outside the image) is an idle step
+  // of pair 0, the longest list; a slot without a ray (past the end; outside the batch in the walk without QUAD) is an idle step
   const long long q_first = (long long)slot * SPLIT_PAIRS;
   const long long n_q = q_first < items ? (items - q_first + stride - 1) / stride : 0;
   const int nhalf = PACK ? 3 : (PER_SAMPLE ? 2 : 2 * nchunks);
@@ -318,8 +359,7 @@ __global__ void __launch_bounds__(SPLIT_THREADS) render_split_kernel(FusedArgs A
 #pragma unroll
             for (int t = 0; t < TR; ++t) {
               SplitRay tr;
-              split_ray_setup<QUAD>(A, q_first + pair0 + t + qi * stride, items, xcd, striped, rows, cw, first_row, per_xcd,
-                              chunks_per_item_ray, tr);
+              split_ray_setup<QUAD>(A, q_first + pair0 + t + qi * stride, items, xcd, striped, rows, cw, first_row, per_xcd, qs, chunks_per_item_ray, tr);
               __builtin_amdgcn_wave_barrier();
               if (lane == 0) {
                 float* w = trec + 16 * t;
@@ -444,17 +484,17 @@ __global__ void __launch_bounds__(SPLIT_THREADS) render_split_kernel(FusedArgs A
             // duo qi = schedule slots 2 qi (ray A) and 2 qi + 1 (ray B): A is set up in the duo's first half-step, B in its second
             // (under the striped schedule a slot in the middle of a pair's list can be empty: either ray may be missing)
             if (k == 0) {
-              split_ray_setup<QUAD>(A, q_first + pair + m + 2 * qi * stride, items, xcd, striped, rows, cw, first_row, per_xcd, chunks_per_item_ray, gr);
+              split_ray_setup<QUAD>(A, q_first + pair + m + 2 * qi * stride, items, xcd, striped, rows, cw, first_row, per_xcd, qs, chunks_per_item_ray, gr);
               if (gr.valid) split_fill_edges(A, gr, (PER_SAMPLE ? gr.chunk : 0) * 64, tb_g, lane);
               gray_b.valid = false;
             }
             if (k == 1) {
-              split_ray_setup<QUAD>(A, q_first + pair + m + (2 * qi + 1) * stride, items, xcd, striped, rows, cw, first_row, per_xcd, chunks_per_item_ray, gray_b);
+              split_ray_setup<QUAD>(A, q_first + pair + m + (2 * qi + 1) * stride, items, xcd, striped, rows, cw, first_row, per_xcd, qs, chunks_per_item_ray, gray_b);
               if (gray_b.valid) split_fill_edges(A, gray_b, (PER_SAMPLE ? gray_b.chunk : 0) * 64, packs + 64 + 68, lane);
             }
           } else {
           if (k == 0)
-            split_ray_setup<QUAD>(A, q_first + pair + m + qi * stride, items, xcd, striped, rows, cw, first_row, per_xcd, chunks_per_item_ray, gr);
+            split_ray_setup<QUAD>(A, q_first + pair + m + qi * stride, items, xcd, striped, rows, cw, first_row, per_xcd, qs, chunks_per_item_ray, gr);
           }
           // early termination: the matrix wave publishes the schedule slot of a ray it has finished early; the rest of
           // that ray's half-steps are then idle for the pair (the workgroup still runs them in lock-step: the time is
@@ -578,7 +618,7 @@ __global__ void __launch_bounds__(SPLIT_THREADS) render_split_kernel(FusedArgs A
         // PACK: k = 0 sets up ray A of the duo (schedule slot 2 qi), k = 1 ray B (slot 2 qi + 1) -- one copy of the code,
         // the ray record and the LDS areas picked by k
         SplitRay cur;
-        split_ray_setup<QUAD>(A, q_first + pair + (PACK ? 2 * qi + k : qi) * stride, items, xcd, striped, rows, cw, first_row, per_xcd, chunks_per_item_ray, cur);
+        split_ray_setup<QUAD>(A, q_first + pair + (PACK ? 2 * qi + k : qi) * stride, items, xcd, striped, rows, cw, first_row, per_xcd, qs, chunks_per_item_ray, cur);
         if (!PACK || k == 0) {
           ray = cur;
           st = CompositeState();
