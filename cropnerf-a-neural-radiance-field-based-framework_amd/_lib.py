@@ -135,6 +135,8 @@ SIGNATURES = {
                                 _P, _P, _P, _P, _P]),
     "cn_field_eval_mp": (C.c_int, [C.POINTER(FieldParams), C.POINTER(Scene), _I32, _I32, _P, _P, _P, _P, _P, _I64, _I32,
                                    _P, _P, _P, _P, _I32, _P]),
+    "cn_field_eval_f16": (C.c_int, [C.POINTER(FieldParams), C.POINTER(Scene), _I32, _I32, _P, _P, _P, _P, _P, _I64, _I32,
+                                    _P, _P, _P, _P, _P]),
     "cn_composite": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _I32, C.POINTER(_F), _I32, _P, _P, _P, _P, _P, _P, _P]),
     "cn_render_workspace_bytes": (C.c_size_t, [C.POINTER(FieldParams)]),
     "cn_render_rays": (C.c_int, [C.POINTER(FieldParams), C.POINTER(Scene), C.POINTER(RenderOpts), _P, _P, _P, _P, _P,
@@ -182,6 +184,9 @@ SIGNATURES = {
     "cn_field_backward_general_ex": (C.c_int, [C.POINTER(FieldParams), C.POINTER(FieldParams), C.POINTER(Scene), _I32,
                                                _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P, _P, C.c_uint32, _P,
                                                C.c_size_t, _P]),
+    "cn_field_backward_general_mp": (C.c_int, [C.POINTER(FieldParams), C.POINTER(FieldParams), C.POINTER(Scene), _I32,
+                                               _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P, _P, C.c_uint32, _I32,
+                                               _P, C.c_size_t, _P]),
     "cn_ray_backward": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _P, _P]),
     "cn_pose_adjustment_backward": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _P, _P]),
     "cn_pose_regularizer": (C.c_int, [_P, _I32, _F, _F, _P, _P, _P]),

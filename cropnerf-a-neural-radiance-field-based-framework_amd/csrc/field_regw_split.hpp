@@ -19,7 +19,15 @@
 //   colour input                  [logit | geo | 0 ... (32) | SH 16 | appearance 32 | 0 ...] (96)
 // so the accumulator rows of the base MLP's second layer go to both buffers at the offset they already have.
 // Density, rgb and the semantic logit leave from the accumulators (the semantic head is a 16 x 64 layer with one real row).
+//
+// F16 = true is the fp16 mode (cn_field_eval_f16): the forward of the reference's mixed-precision training class.  The same
+// ownership and layout with ONE 16-bit image per operand -- weights and activations rounded to fp16 (nearest even) once, by
+// their loader or producer, in the hi half of each buffer (the lo half stays unused) -- and one v_mfma_f32_16x16x32_f16 per
+// 32-wide K block instead of three bf16 products.  Those are the roundings the mixed-precision general backward recomputes
+// (train_field_general.hpp, MM = 1), so the ReLU gates of the forward and of the recompute agree.
 #pragma once
+
+#include <type_traits>
 
 namespace cn {
 namespace rws {
@@ -27,6 +35,8 @@ namespace rws {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 constexpr int TS = 64, NT = 512, NW = 8;
 
 constexpr int pad16(int n) { return (n + 15) & ~15; }
@@ -49,6 +59,7 @@ __device__ __forceinline__ int col_of(int k, int K) {
 // A operands of one row tile: lane (i = lane & 15, q = lane >> 4) holds W[16 rt + i][32 kb + 8 q + e], e = 0..7, as hi and lo
 template <int KP>
 struct RowTile {
+  static constexpr bool F16 = false;
   bf16x8 hi[KP / 32], lo[KP / 32];
   template <ColMap M, int GEO>
   __device__ __forceinline__ void load(const float* __restrict__ W, int N, int K, int wave, int lane) {
@@ -67,6 +78,28 @@ struct RowTile {
     }
   }
 };
+
+// the fp16 mode's A operands: the same elements, rounded to fp16 once
+template <int KP>
+struct RowTileH {
+  static constexpr bool F16 = true;
+  f16x8 h[KP / 32];
+  template <ColMap M, int GEO>
+  __device__ __forceinline__ void load(const float* __restrict__ W, int N, int K, int wave, int lane) {
+    const int ntiles = pad16(N) / 16;
+    const int i = lane & 15, q = lane >> 4, n = 16 * (wave % ntiles) + i;
+#pragma unroll
+    for (int kb = 0; kb < KP / 32; ++kb) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int c = col_of<M, GEO>(32 * kb + 8 * q + e, K);
+        h[kb][e] = (_Float16)((n < N && c >= 0) ? W[(size_t)n * K + c] : 0.f);
+      }
+    }
+  }
+};
+template <int KP, bool F16>
+using RowTileT = typename std::conditional<F16, RowTileH<KP>, RowTile<KP>>::type;
 
 struct SplitBuf {
   __bf16* hi;
@@ -90,6 +123,20 @@ __device__ __forceinline__ void store_split1(const SplitBuf& b, int s, int k, fl
   const __bf16 x = (__bf16)v;
   b.hi[s * b.stride + k] = x;
   b.lo[s * b.stride + k] = (__bf16)(v - (float)x);
+}
+// the same in the buffer's form of the mode (F16: one fp16 value in the hi half)
+template <bool F16>
+__device__ __forceinline__ void store4(const SplitBuf& b, int s, int k0, const f32x4& v) {
+  if (!F16) return store_split4(b, s, k0, v);
+  f16x4 h;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) h[r] = (_Float16)v[r];
+  *reinterpret_cast<f16x4*>(reinterpret_cast<_Float16*>(b.hi) + s * b.stride + k0) = h;
+}
+template <bool F16>
+__device__ __forceinline__ void store1(const SplitBuf& b, int s, int k, float v) {
+  if (!F16) return store_split1(b, s, k, v);
+  reinterpret_cast<_Float16*>(b.hi)[s * b.stride + k] = (_Float16)v;
 }
 
 // the column tiles (16 samples each) of this wave for a layer with `ntiles` row tiles (as field_regw.hpp)
@@ -115,6 +162,16 @@ __device__ __forceinline__ f32x4 block(const RowTile<KP>& rt, const SplitBuf& in
   return acc;
 }
 
+template <int KP>
+__device__ __forceinline__ f32x4 block(const RowTileH<KP>& rt, const SplitBuf& in, int ct, f32x4 acc, int lane) {
+  const int i = lane & 15, q = lane >> 4;
+  const _Float16* ph = reinterpret_cast<const _Float16*>(in.hi) + (16 * ct + i) * in.stride + 8 * q;
+#pragma unroll
+  for (int kb = 0; kb < KP / 32; ++kb)
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(rt.h[kb], *reinterpret_cast<const f16x8*>(ph + 32 * kb), acc, 0, 0, 0);
+  return acc;
+}
+
 __device__ __forceinline__ f32x4 bias4(const float* __restrict__ bias, int N, int rt0, int lane) {
   const int q = lane >> 4;
   f32x4 b;
@@ -128,8 +185,8 @@ __device__ __forceinline__ f32x4 bias4(const float* __restrict__ bias, int N, in
 
 // out = act(b + W in), split, for this wave's (row tile, column tiles); rows >= N come out as zeros.  `out2` (optional)
 // receives the same rows at the same offsets (the base MLP's output feeds two inputs).
-template <int KP, bool RELU>
-__device__ __forceinline__ void layer(const RowTile<KP>& rt, const float* __restrict__ bias, int N, const SplitBuf& in,
+template <int KP, bool RELU, class RT>
+__device__ __forceinline__ void layer(const RT& rt, const float* __restrict__ bias, int N, const SplitBuf& in,
                                       const SplitBuf& out, const SplitBuf* out2, int wave, int lane) {
   const int ntiles = pad16(N) / 16, rt0 = 16 * (wave % ntiles);
   int ct_lo, ct_hi;
@@ -143,12 +200,12 @@ __device__ __forceinline__ void layer(const RowTile<KP>& rt, const float* __rest
 #pragma unroll
       for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
     }
-    store_split4(out, 16 * ct + i, rt0 + 4 * q, v);
-    if (out2) store_split4(*out2, 16 * ct + i, rt0 + 4 * q, v);
+    store4<RT::F16>(out, 16 * ct + i, rt0 + 4 * q, v);
+    if (out2) store4<RT::F16>(*out2, 16 * ct + i, rt0 + 4 * q, v);
   }
 }
 
-template <int GEO, int NS, int SW>
+template <int GEO, int NS, int SW, bool F16 = false>
 __global__ void __launch_bounds__(NT)
 field_eval_regw_split_kernel(FieldDev fp, SceneDev sc, int app_mode, int sh_unit, const float* __restrict__ origins,
                              const float* __restrict__ directions, const int64_t* __restrict__ cam_idx,
@@ -186,15 +243,15 @@ field_eval_regw_split_kernel(FieldDev fp, SceneDev sc, int app_mode, int sh_unit
     app_mean[tid] = m / (float)fp.num_images;
   }
   // ---- the weights of this wave's row tiles, split, for the whole kernel ----------------------------------------------------
-  RowTile<32> w_b0;
-  RowTile<64> w_b1;
-  RowTile<32> w_s0;
-  RowTile<SWP> w_s1;
-  RowTile<SWP> w_s2;  // third semantic layer (NS == 3)
-  RowTile<64> w_sh;   // semantic head: one real row
-  RowTile<96> w_c0;
-  RowTile<64> w_c1;
-  RowTile<64> w_c2;
+  RowTileT<32, F16> w_b0;
+  RowTileT<64, F16> w_b1;
+  RowTileT<32, F16> w_s0;
+  RowTileT<SWP, F16> w_s1;
+  RowTileT<SWP, F16> w_s2;  // third semantic layer (NS == 3)
+  RowTileT<64, F16> w_sh;   // semantic head: one real row
+  RowTileT<96, F16> w_c0;
+  RowTileT<64, F16> w_c1;
+  RowTileT<64, F16> w_c2;
   w_b0.template load<MAP_IDENT, GEO>(fp.base.w[0], H, 32, wave, lane);
   w_b1.template load<MAP_IDENT, GEO>(fp.base.w[1], NG, H, wave, lane);
   w_s0.template load<MAP_SEM0, GEO>(fp.sem.w[0], SW, GEO, wave, lane);
@@ -229,8 +286,8 @@ field_eval_regw_split_kernel(FieldDev fp, SceneDev sc, int app_mode, int sh_unit
     for (int h = 0; h < 2; ++h) {
       const int l = grp + NW * h;
       const float2 f = hash_level_any(fp.grid, l, px, py, pz);
-      store_split1(ENC, s, 2 * l, f.x);
-      store_split1(ENC, s, 2 * l + 1, f.y);
+      store1<F16>(ENC, s, 2 * l, f.x);
+      store1<F16>(ENC, s, 2 * l + 1, f.y);
     }
     if (rgb) {
       if (grp == 1) {
@@ -243,7 +300,7 @@ field_eval_regw_split_kernel(FieldDev fp, SceneDev sc, int app_mode, int sh_unit
         float sh[16];
         sh_deg4(sx, sy, sz, sh);
 #pragma unroll
-        for (int k = 0; k < 16; k += 4) store_split4(C, s, 32 + k, f32x4{sh[k], sh[k + 1], sh[k + 2], sh[k + 3]});
+        for (int k = 0; k < 16; k += 4) store4<F16>(C, s, 32 + k, f32x4{sh[k], sh[k + 1], sh[k + 2], sh[k + 3]});
       }
       const float* emb = app_mode == CN_APP_PER_CAMERA ? fp.appearance + cam_idx[r] * (long long)APP : nullptr;
       {  // four appearance columns per wave
@@ -253,7 +310,7 @@ field_eval_regw_split_kernel(FieldDev fp, SceneDev sc, int app_mode, int sh_unit
           const int k = 4 * grp + e;
           a[e] = app_mode == CN_APP_MEAN ? app_mean[k] : (emb ? emb[k] : 0.f);
         }
-        store_split4(C, s, 48 + 4 * grp, a);
+        store4<F16>(C, s, 48 + 4 * grp, a);
       }
     }
     __syncthreads();
@@ -269,8 +326,8 @@ field_eval_regw_split_kernel(FieldDev fp, SceneDev sc, int app_mode, int sh_unit
       for (int ct = ct_lo; ct < ct_hi; ++ct) {
         const f32x4 v = block<64>(w_b1, X, ct, b4, lane);
         const int sc_ = 16 * ct + i;
-        store_split4(G, sc_, rt0 + 4 * q, v);
-        if (rgb) store_split4(C, sc_, rt0 + 4 * q, v);
+        store4<F16>(G, sc_, rt0 + 4 * q, v);
+        if (rgb) store4<F16>(C, sc_, rt0 + 4 * q, v);
         if (density && rt0 == 0 && q == 0 && tile * TS + sc_ < total) density[tile * TS + sc_] = expf(v[0]) * selv[sc_];
       }
     }

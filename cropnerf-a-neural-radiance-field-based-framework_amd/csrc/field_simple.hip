@@ -578,6 +578,48 @@ extern "C" int cn_field_eval_mp(const cn_field_params* params, const cn_scene* s
   return cn::check_launch("cn_field_eval");
 }
 
+extern "C" int cn_field_eval_f16(const cn_field_params* params, const cn_scene* scene, int32_t app_mode, int32_t sh_unit_dir,
+                                 const float* origins, const float* directions, const int64_t* camera_indices,
+                                 const float* starts, const float* ends, int64_t num_rays, int32_t num_samples, float* density,
+                                 float* rgb, float* semantics, float* positions, cn_stream_t stream) {
+  CN_REQUIRE(params && scene && origins && directions && starts && ends, CN_ERR_INVALID, "cn_field_eval_f16: null input");
+  CN_REQUIRE(num_samples > 0, CN_ERR_INVALID, "cn_field_eval_f16: num_samples must be > 0");
+  CN_REQUIRE(app_mode >= CN_APP_ZEROS && app_mode <= CN_APP_PER_CAMERA, CN_ERR_INVALID, "cn_field_eval_f16: app_mode %d",
+             app_mode);
+  CN_REQUIRE(app_mode != CN_APP_PER_CAMERA || camera_indices, CN_ERR_INVALID, "Camera indices are not provided.");
+  int rc = cn::validate_field(*params);
+  if (rc) return rc;
+  // the fp16 mode of field_regw_split.hpp exists for the two field shapes of the reference's configs only
+  const bool def = cn::rw::regw_shape_matches<15, 2, 64>(*params), big = cn::rw::regw_shape_matches<30, 3, 128>(*params);
+  CN_REQUIRE(def || big, CN_ERR_UNSUPPORTED,
+             "cn_field_eval_f16: built for the fruit_nerf_method and fruit_nerf_method_big / _huge field shapes only");
+  if (num_rays <= 0) return CN_OK;
+  static cn::PerDevice<int> attrs;
+  rc = attrs.get(
+      [&](int, int&) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(cn::rws::field_eval_regw_split_kernel<15, 2, 64, true>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)cn::rws::LDS_BYTES);
+        if (e != hipSuccess) return e;
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(cn::rws::field_eval_regw_split_kernel<30, 3, 128, true>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)cn::rws::LDS_BYTES);
+      },
+      nullptr, "cn_field_eval_f16");
+  if (rc) return rc;
+  const long long ntiles = (num_rays * (long long)num_samples + cn::rws::TS - 1) / cn::rws::TS;
+  const dim3 grid(cn::grid_for(ntiles, 1, 256)), block(cn::rws::NT);
+  if (def)
+    hipLaunchKernelGGL((cn::rws::field_eval_regw_split_kernel<15, 2, 64, true>), grid, block, cn::rws::LDS_BYTES,
+                       cn::as_stream(stream), cn::make_field_dev(*params), cn::make_scene_dev(*scene), app_mode, sh_unit_dir,
+                       origins, directions, camera_indices, starts, ends, (long long)num_rays, num_samples, density, rgb,
+                       semantics, positions);
+  else
+    hipLaunchKernelGGL((cn::rws::field_eval_regw_split_kernel<30, 3, 128, true>), grid, block, cn::rws::LDS_BYTES,
+                       cn::as_stream(stream), cn::make_field_dev(*params), cn::make_scene_dev(*scene), app_mode, sh_unit_dir,
+                       origins, directions, camera_indices, starts, ends, (long long)num_rays, num_samples, density, rgb,
+                       semantics, positions);
+  return cn::check_launch("cn_field_eval_f16");
+}
+
 extern "C" int cn_proposal_density(const cn_density_params* params, const cn_scene* scene, const float* origins,
                                    const float* directions, const float* starts, const float* ends, int64_t num_rays,
                                    int32_t num_samples, float* density, cn_stream_t stream) {

@@ -1400,8 +1400,23 @@ extern "C" int cn_field_backward_general_ex(const cn_field_params* params, const
                                             int64_t num_rays, int32_t num_samples, float* d_positions,
                                             float* d_directions, uint32_t flags, void* workspace, size_t workspace_bytes,
                                             cn_stream_t stream) {
+  return cn_field_backward_general_mp(params, grads, scene, app_mode, sh_unit_dir, app_mean, origins, directions, camera_indices,
+                                      starts, ends, d_density, d_rgb, d_semantics, num_rays, num_samples, d_positions,
+                                      d_directions, flags, CN_MATRIX_FP32, workspace, workspace_bytes, stream);
+}
+
+extern "C" int cn_field_backward_general_mp(const cn_field_params* params, const cn_field_params* grads,
+                                            const cn_scene* scene, int32_t app_mode, int32_t sh_unit_dir,
+                                            const float* app_mean, const float* origins, const float* directions,
+                                            const int64_t* camera_indices, const float* starts, const float* ends,
+                                            const float* d_density, const float* d_rgb, const float* d_semantics,
+                                            int64_t num_rays, int32_t num_samples, float* d_positions,
+                                            float* d_directions, uint32_t flags, int32_t matrix_precision, void* workspace,
+                                            size_t workspace_bytes, cn_stream_t stream) {
   CN_REQUIRE(params && grads && scene && origins && directions && starts && ends && d_density && d_rgb && d_semantics,
              CN_ERR_INVALID, "cn_field_backward_general: null argument");
+  CN_REQUIRE(matrix_precision == CN_MATRIX_FP32 || matrix_precision == CN_MATRIX_SPLIT_BF16 || matrix_precision == CN_MATRIX_F16,
+             CN_ERR_INVALID, "cn_field_backward_general: matrix_precision %d", matrix_precision);
   CN_REQUIRE(app_mode != CN_APP_PER_CAMERA || camera_indices, CN_ERR_INVALID, "Camera indices are not provided.");
   CN_REQUIRE(app_mode != CN_APP_MEAN || app_mean, CN_ERR_INVALID, "cn_field_backward_general: app_mean required");
   CN_REQUIRE((flags & ~cn::TRAIN_FLAGS_ALL) == 0, CN_ERR_INVALID, "cn_field_backward_general: unknown flags 0x%x",
@@ -1504,8 +1519,12 @@ extern "C" int cn_field_backward_general_ex(const cn_field_params* params, const
   A.S = num_samples;
   A.pass_sem = (flags & CN_TRAIN_PASS_SEMANTIC_GRADIENTS) ? 1 : 0;
   CN_REQUIRE(A.g_table && (!A.app_per_camera || A.g_emb), CN_ERR_INVALID, "cn_field_backward_general: null gradient buffer");
+  // CN_MATRIX_F16: the mixed-precision kernel; CN_MATRIX_SPLIT_BF16 (a ~fp32 forward) trains in exact fp32, as cn_field_backward
+  const bool mixed = matrix_precision == CN_MATRIX_F16;
+  const void* kernel = mixed ? reinterpret_cast<const void*>(cn::gb::field_backward_general_kernel<1>)
+                             : reinterpret_cast<const void*>(cn::gb::field_backward_general_kernel<0>);
   // (the LDS need depends on the field shape, so the attribute is set per call: cheap, and correct on every device)
-  CN_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(cn::gb::field_backward_general_kernel),
+  CN_REQUIRE(hipFuncSetAttribute(kernel,
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess,
              CN_ERR_LAUNCH, "cn_field_backward_general: hipFuncSetAttribute(MaxDynamicSharedMemorySize, %zu) failed", lds);
   CN_REQUIRE(hipMemsetAsync(workspace, 0, (size_t)nblk * ppb * sizeof(float), s) == hipSuccess, CN_ERR_LAUNCH,
@@ -1521,7 +1540,10 @@ extern "C" int cn_field_backward_general_ex(const cn_field_params* params, const
                                       (unsigned long long)num_rays * (unsigned long long)num_samples);
     if (A.cells.num_levels > 0) A.coarse.base = nullptr;
   }
-  hipLaunchKernelGGL(cn::gb::field_backward_general_kernel, dim3(grid), dim3(cn::gb::NTG), lds, s, A);
+  if (mixed)
+    hipLaunchKernelGGL(cn::gb::field_backward_general_kernel<1>, dim3(grid), dim3(cn::gb::NTG), lds, s, A);
+  else
+    hipLaunchKernelGGL(cn::gb::field_backward_general_kernel<0>, dim3(grid), dim3(cn::gb::NTG), lds, s, A);
   CN_DET_FLUSH(s);
   cn::launch_coarse_reduce(A.coarse, A.grid, A.g_table, s);
   cn::launch_cell_fold(A.cells, A.grid, A.g_table, s);

@@ -10,6 +10,14 @@
 // workgroup ([workgroups][parameters] floats in the caller's workspace); field_backward_reduce_kernel folds the scratch
 // into the gradient tensors afterwards.  Hash-table and appearance-embedding gradients are scatter-adds as in the
 // specialised kernel, and so are the optional position / direction gradients for the camera pose refinement.
+//
+// Matrix modes (template parameter MM, as train_field_mfma.hpp's): 0 = exact fp32 (v_mfma_f32_16x16x4_f32 chains), 1 = the
+// reference's mixed-precision class (cn_field_backward_general_mp, CN_MATRIX_F16): the forward recompute on
+// v_mfma_f32_16x16x16_f16 -- weights and layer inputs rounded to fp16 (nearest even) as they become operands, fp32 sums, the
+// function cn_field_eval_f16 computes -- and the gradient products dX = W^T dY, dW += dY X^T on v_mfma_f32_16x16x16_bf16.  A
+// lane's four k-steps of the fp32 chain ARE the four-element operand of the 16 x 16 x 16 instruction, so every read stays
+// where it is and one matrix instruction replaces four.  Table masters are read unrounded; the interpolated feature is
+// rounded once, as the first layer's input.  Scratch slices, the reduction and the scatters are the same in both modes.
 #pragma once
 
 namespace cn {
@@ -66,7 +74,7 @@ __device__ __forceinline__ int opaque_i(int v) {
 // tile `wave` and BOTH halves: its 32 A operands are loaded once and feed two accumulation chains (half the weight loads, half
 // the L1 line lookups, one exposed L2 latency per phase instead of two, and two independent matrix chains).  With fewer row
 // tiles the 2 T blocks are spread over the waves one (row tile, half) each, as before.
-template <bool BOTH>
+template <bool BOTH, int MM>
 __device__ __forceinline__ void gen_fwd_blocks(const GenLayer& L, const float* in, float* out, bool relu, int first, int step,
                                                int count, int i, int q, int Kp) {
   for (int blk = first; blk < count; blk += step) {
@@ -100,7 +108,18 @@ __device__ __forceinline__ void gen_fwd_blocks(const GenLayer& L, const float* i
     }
 #pragma unroll
     for (int kb = 0; kb < 8; ++kb) {
-      if (16 * kb < Kp) {
+      if (MM == 1 && 16 * kb < Kp) {
+        f32x4 a, b0, b1;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float* row = in + (16 * kb + 4 * q + e) * LDG + s0 + i;
+          a[e] = areg[4 * kb + e];
+          b0[e] = row[0];
+          if (BOTH) b1[e] = row[16];
+        }
+        acc0 = mf::mfma_f16x4(a, b0, acc0);
+        if (BOTH) acc1 = mf::mfma_f16x4(a, b1, acc1);
+      } else if (16 * kb < Kp) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const float* row = in + (16 * kb + 4 * q + e) * LDG + s0 + i;
@@ -123,16 +142,17 @@ __device__ __forceinline__ void gen_fwd_blocks(const GenLayer& L, const float* i
 }
 
 // out[n][s] = act(b[n] + sum_k W[n][k] in[k][s]) for all n < pad16(N); rows >= N come out as zeros
+template <int MM>
 __device__ __forceinline__ void gen_fwd(const GenLayer& L, const float* in, float* out, bool relu, int tid) {
   const int lane = opaque_i(tid) & 63, wave = tid >> 6, i = lane & 15, q = lane >> 4;
   const int Kp = (L.K + 15) & ~15, tiles = ((L.N + 15) & ~15) >> 4;
   if (tiles >= NTG / 64)
-    gen_fwd_blocks<true>(L, in, out, relu, wave, NTG / 64, tiles, i, q, Kp);
+    gen_fwd_blocks<true, MM>(L, in, out, relu, wave, NTG / 64, tiles, i, q, Kp);
   else
-    gen_fwd_blocks<false>(L, in, out, relu, wave, NTG / 64, 2 * tiles, i, q, Kp);
+    gen_fwd_blocks<false, MM>(L, in, out, relu, wave, NTG / 64, 2 * tiles, i, q, Kp);
 }
 
-template <bool BOTH>
+template <bool BOTH, int MM>
 __device__ __forceinline__ void gen_bwd_blocks(const GenLayer& L, const float* dy, float* dx, const float* mask, int first,
                                                int step, int count, int i, int q, int Np) {
   for (int blk = first; blk < count; blk += step) {
@@ -147,7 +167,18 @@ __device__ __forceinline__ void gen_bwd_blocks(const GenLayer& L, const float* d
     }
 #pragma unroll
     for (int nb = 0; nb < 8; ++nb) {
-      if (16 * nb < Np) {
+      if (MM == 1 && 16 * nb < Np) {
+        f32x4 a, b0, b1;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float* row = dy + (16 * nb + 4 * q + e) * LDG + s0 + i;
+          a[e] = areg[4 * nb + e];
+          b0[e] = row[0];
+          if (BOTH) b1[e] = row[16];
+        }
+        acc0 = mf::mfma_bf16x4(a, b0, acc0);
+        if (BOTH) acc1 = mf::mfma_bf16x4(a, b1, acc1);
+      } else if (16 * nb < Np) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const float* row = dy + (16 * nb + 4 * q + e) * LDG + s0 + i;
@@ -171,16 +202,18 @@ __device__ __forceinline__ void gen_bwd_blocks(const GenLayer& L, const float* d
 }
 
 // dx[k][s] = (sum_n W[n][k] dy[n][s]) * (mask ? mask[k][s] > 0 : 1) for all k < pad16(K)
+template <int MM>
 __device__ __forceinline__ void gen_bwd(const GenLayer& L, const float* dy, float* dx, const float* mask, int tid) {
   const int lane = opaque_i(tid) & 63, wave = tid >> 6, i = lane & 15, q = lane >> 4;
   const int tiles = ((L.K + 15) & ~15) >> 4, Np = (L.N + 15) & ~15;
   if (tiles >= NTG / 64)
-    gen_bwd_blocks<true>(L, dy, dx, mask, wave, NTG / 64, tiles, i, q, Np);
+    gen_bwd_blocks<true, MM>(L, dy, dx, mask, wave, NTG / 64, tiles, i, q, Np);
   else
-    gen_bwd_blocks<false>(L, dy, dx, mask, wave, NTG / 64, 2 * tiles, i, q, Np);
+    gen_bwd_blocks<false, MM>(L, dy, dx, mask, wave, NTG / 64, 2 * tiles, i, q, Np);
 }
 
 // scratch dW[n][k] += sum_s dy[n][s] x[k][s];  scratch db[n] += sum_s dy[n][s]   (workgroup-private, no atomics)
+template <int MM>
 __device__ __forceinline__ void gen_dw(const GenLayer& L, const float* dy, const float* x, float* scratch, int tid) {
   const int lane = opaque_i(tid) & 63, wave = tid >> 6, i = lane & 15, q = lane >> 4;
   const int Kp = (L.K + 15) & ~15, Np = (L.N + 15) & ~15;
@@ -195,6 +228,10 @@ __device__ __forceinline__ void gen_dw(const GenLayer& L, const float* dy, const
     for (int sb = 0; sb < TSG; sb += 16) {
       const f32x4 a = *reinterpret_cast<const f32x4*>(dy + (n0 + i) * LDG + sb + 4 * q);
       const f32x4 b = *reinterpret_cast<const f32x4*>(x + (k0 + i) * LDG + sb + 4 * q);
+      if (MM == 1) {
+        acc = mf::mfma_bf16x4(a, b, acc);
+        continue;
+      }
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float av = a[e], bv = b[e];
@@ -240,6 +277,7 @@ __device__ __forceinline__ void gen_dw(const GenLayer& L, const float* dy, const
   }
 }
 
+template <int MM>
 __global__ void __launch_bounds__(NTG) field_backward_general_kernel(GenArgs A) {
   extern __shared__ __align__(16) float lds[];
   const int tid = threadIdx.x;
@@ -306,25 +344,25 @@ __global__ void __launch_bounds__(NTG) field_backward_general_kernel(GenArgs A) 
     }
     __syncthreads();
     // ---- forward ---------------------------------------------------------------------------------------------------------
-    gen_fwd(A.base[0], ENC, H1, true, tid);
+    gen_fwd<MM>(A.base[0], ENC, H1, true, tid);
     __syncthreads();
-    gen_fwd(A.base[1], H1, G, false, tid);
+    gen_fwd<MM>(A.base[1], H1, G, false, tid);
     __syncthreads();
     for (int k = grp; k < A.geo; k += 16) CIN[(16 + k) * LDG + s] = G[(1 + k) * LDG + s];
     {
       const float* x = G + LDG;  // geo rows (detached input of the semantic MLP)
       for (int l = 0; l < A.ns; ++l) {
         float* y = lds + A.r_s[l] * LDG;
-        gen_fwd(A.sem[l], x, y, l < A.ns - 1, tid);
+        gen_fwd<MM>(A.sem[l], x, y, l < A.ns - 1, tid);
         __syncthreads();
         x = y;
       }
     }
-    gen_fwd(A.col[0], CIN, C1, true, tid);
+    gen_fwd<MM>(A.col[0], CIN, C1, true, tid);
     __syncthreads();
-    gen_fwd(A.col[1], C1, C2, true, tid);
+    gen_fwd<MM>(A.col[1], C1, C2, true, tid);
     __syncthreads();
-    gen_fwd(A.col[2], C2, RGB, false, tid);
+    gen_fwd<MM>(A.col[2], C2, RGB, false, tid);
     __syncthreads();
     // ---- semantic branch backward (stops at the detached geo features; with pass_sem its input gradient W_s0^T d_s1 goes to
     //      DG rows 0..geo-1, which nothing touches before the d(base output) assembly) ----------------------------------------
@@ -348,9 +386,9 @@ __global__ void __launch_bounds__(NTG) field_backward_general_kernel(GenArgs A) 
       float* dnext = DB;
       for (int l = A.ns - 1; l >= 0; --l) {
         const float* xin = l == 0 ? G + LDG : lds + A.r_s[l - 1] * LDG;
-        gen_dw(A.sem[l], dcur, xin, scratch, tid);
-        if (l > 0) gen_bwd(A.sem[l], dcur, dnext, xin, tid);  // gate: the input is a post-ReLU activation
-        else if (A.pass_sem) gen_bwd(A.sem[0], dcur, DG, nullptr, tid);
+        gen_dw<MM>(A.sem[l], dcur, xin, scratch, tid);
+        if (l > 0) gen_bwd<MM>(A.sem[l], dcur, dnext, xin, tid);  // gate: the input is a post-ReLU activation
+        else if (A.pass_sem) gen_bwd<MM>(A.sem[0], dcur, DG, nullptr, tid);
         __syncthreads();
         float* t = dcur;
         dcur = dnext;
@@ -364,14 +402,14 @@ __global__ void __launch_bounds__(NTG) field_backward_general_kernel(GenArgs A) 
       DRGB[row * LDG + s] = valid ? A.d_rgb[3 * ic + row] * sg * (1.f - sg) : 0.f;
     }
     __syncthreads();
-    gen_dw(A.col[2], DRGB, C2, scratch, tid);
-    gen_bwd(A.col[2], DRGB, DA, C2, tid);
+    gen_dw<MM>(A.col[2], DRGB, C2, scratch, tid);
+    gen_bwd<MM>(A.col[2], DRGB, DA, C2, tid);
     __syncthreads();
-    gen_dw(A.col[1], DA, C1, scratch, tid);
-    gen_bwd(A.col[1], DA, DB, C1, tid);
+    gen_dw<MM>(A.col[1], DA, C1, scratch, tid);
+    gen_bwd<MM>(A.col[1], DA, DB, C1, tid);
     __syncthreads();
-    gen_dw(A.col[0], DB, CIN, scratch, tid);
-    gen_bwd(A.col[0], DB, DCIN, nullptr, tid);
+    gen_dw<MM>(A.col[0], DB, CIN, scratch, tid);
+    gen_bwd<MM>(A.col[0], DB, DCIN, nullptr, tid);
     __syncthreads();
     // ---- d(base output): row 0 = density logit through trunc_exp and the selector, rows 1..geo from the colour input ----
     // (with pass_sem plus the semantic MLP's share, which sits one row up in DG: read before anyone writes DG)
@@ -426,11 +464,11 @@ __global__ void __launch_bounds__(NTG) field_backward_general_kernel(GenArgs A) 
       }
     }
     __syncthreads();
-    gen_dw(A.base[1], DG, H1, scratch, tid);
-    gen_bwd(A.base[1], DG, DA, H1, tid);
+    gen_dw<MM>(A.base[1], DG, H1, scratch, tid);
+    gen_bwd<MM>(A.base[1], DG, DA, H1, tid);
     __syncthreads();
-    gen_dw(A.base[0], DA, ENC, scratch, tid);
-    gen_bwd(A.base[0], DA, DB, nullptr, tid);
+    gen_dw<MM>(A.base[0], DA, ENC, scratch, tid);
+    gen_bwd<MM>(A.base[0], DA, DB, nullptr, tid);
     __syncthreads();
     // ---- hash-table gradient (16 consecutive lanes = 16 consecutive samples of one level: run-length pre-reduction) ----
     float gpx = 0.f, gpy = 0.f, gpz = 0.f;

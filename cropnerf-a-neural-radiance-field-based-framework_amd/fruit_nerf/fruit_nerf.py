@@ -270,11 +270,14 @@ class FruitModel:
         reference's own training arithmetic -- ``mixed_precision=True`` on tiny-cuda-nn's fp16 modules
         (``fruit_nerf_config.py:35``, ``fruit_field.py:95,125-167``): the field's forward and its backward recompute with fp16
         operands, gradient products in bf16, fp32 sums, fp32 master parameters and Adam (``cn_field_backward_mp``).  The field
-        shapes of the ``_big`` / ``_huge`` methods (shape-generic kernels) and the proposal networks train in fp32 whatever the
-        setting."""
+        shapes of the ``_big`` / ``_huge`` methods train in the same class through the shape-generic kernels
+        (``cn_field_eval_f16`` + ``cn_field_backward_general_mp``); a generic shape that ``cn_field_eval_f16`` is not built
+        for, and the proposal networks, train in fp32 whatever the setting."""
         mode = self._matrix_mode()
-        if mode != "f16" or not self._fused_shape:
+        if mode != "f16":
             return L.MATRIX_FP32  # "split_bf16" is an arithmetic of the eval renders: training stays exact fp32
+        if not self._fused_shape and not ops.field_eval_f16_supported(self.field_spec):
+            return L.MATRIX_FP32
         return L.MATRIX_F16
 
     def _opts(self, num_samples: int, density_only: bool = False) -> L.RenderOpts:

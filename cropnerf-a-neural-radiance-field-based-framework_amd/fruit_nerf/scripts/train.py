@@ -229,7 +229,9 @@ def entrypoint(argv=None):
                          "torch modules.  Default: the method specification's")
     ap.add_argument("--matrix-precision", choices=["fp32", "f16", "split_bf16"], default=None,
                     help="matrix arithmetic of the field in training: fp32 (default, exact), f16 = the reference's mixed-precision "
-                         "class (fp16 forward operands, bf16 gradient products, fp32 sums and masters), split_bf16 (forward only)")
+                         "class (fp16 forward operands, bf16 gradient products, fp32 sums and masters) for the field of every "
+                         "method specification (fruit_nerf, fruit_nerf_big, fruit_nerf_huge; the proposal networks stay fp32), "
+                         "split_bf16 (forward only)")
     a = ap.parse_args(argv)
     return train(a.method, a.data, a.output_dir, a.max_num_iterations, a.steps_per_save, a.downscale_factor,
                  a.experiment_name, a.timestamp, a.seed, a.log_every, a.train_split_fraction, load_dir=a.load_dir,

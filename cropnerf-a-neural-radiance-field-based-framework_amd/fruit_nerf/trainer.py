@@ -6,7 +6,9 @@ per-camera appearance) -> ``get_loss_dict`` (``fruit_nerf/fruit_nerf.py:601-615`
 -> backward -> Adam with exponential LR decay (``fruit_nerf/fruit_nerf_config.py:45-60``) -> anneal callback
 (``fruit_nerf.py:198-232``).
 
-``fruit_nerf_method_big`` / ``_huge`` (other field shapes) train through the shape-generic kernels.  The camera pose refinement (``camera_opt`` group, ``fruit_nerf.py:195``) is trained too: the field / proposal backward
+``fruit_nerf_method_big`` / ``_huge`` (other field shapes) train through the shape-generic kernels, in either arithmetic:
+``cn_field_eval`` + ``cn_field_backward_general`` in fp32, ``cn_field_eval_f16`` + ``cn_field_backward_general_mp`` in the
+mixed-precision class.  The camera pose refinement (``camera_opt`` group, ``fruit_nerf.py:195``) is trained too: the field / proposal backward
 kernels return d loss / d sample position (and the SH-input gradient of the colour branch), ``cn_ray_backward`` reduces
 them per ray and ``cn_pose_adjustment_backward`` chains through exp_map_SO3xR3; ``camera_opt_regularizer``
 (``fruit_nerf.py:614``) is added by ``cn_pose_regularizer``.  The proposal networks follow the reference's update
@@ -85,7 +87,7 @@ class FruitTrainer:
             raise NotImplementedError(f"training with background_color={model.config.background_color!r}: the training kernels "
                                       "implement 'last_sample' (the reference's setting); other backgrounds are eval-only")
         # fruit_nerf_method_big / _huge field shapes train through the shape-generic kernels (cn_field_eval +
-        # cn_field_backward_general)
+        # cn_field_backward_general; cn_field_eval_f16 + cn_field_backward_general_mp in the mixed-precision class)
         self.general = not model._fused_shape
         # the semantic loss through the weights and the geo features (fruit_nerf.py:586-590, fruit_field.py:264-266) and
         # nerfstudio's distance-squared gradient scaling (fruit_nerf.py:553-554): flags of the backward kernels, fixed from here on
@@ -267,7 +269,11 @@ class FruitTrainer:
         # ---- field forward (fused kernel, per-sample outputs) --------------------------------------------------------
         S = cfg.num_nerf_samples_per_ray
         mp = m.train_matrix_precision()  # fp32, or the reference's mixed-precision class (config.matrix_precision = "f16")
-        if self.general:
+        if self.general and mp == L.MATRIX_F16:
+            # the fp16 forward whose roundings the mixed-precision backward recomputes (the ReLU gates agree)
+            fo = ops.field_eval_f16(m.field, scene, o, d, cam, starts, ends, app_mode=L.APP_PER_CAMERA,
+                                    sh_unit_dir=cfg.sh_input == "unit")
+        elif self.general:
             fo = ops.field_eval(m.field, scene, o, d, cam, starts, ends, app_mode=L.APP_PER_CAMERA,
                                 sh_unit_dir=cfg.sh_input == "unit")
         else:
@@ -289,7 +295,8 @@ class FruitTrainer:
                 self._general_ws = ops.field_backward_general(
                     m.field, self.grad_field, scene, o, d, cam, starts, ends, rb_out["d_density"], rb_out["d_rgb"],
                     rb_out["d_semantics"], app_mode=L.APP_PER_CAMERA, sh_unit_dir=cfg.sh_input == "unit",
-                    workspace=self._general_ws, d_positions=dpos, d_directions=ddir, flags=self.train_flags)
+                    workspace=self._general_ws, d_positions=dpos, d_directions=ddir, flags=self.train_flags,
+                    matrix_precision=mp)
             else:
                 ops.field_backward(m.field, self.grad_field, scene, o, d, cam, starts, ends, rb_out["d_density"],
                                    rb_out["d_rgb"], rb_out["d_semantics"], app_mode=L.APP_PER_CAMERA,

@@ -616,6 +616,39 @@ def field_eval(fh: FieldHandle, scene: L.Scene, origins: Tensor, directions: Ten
     return out
 
 
+def field_eval_f16(fh: FieldHandle, scene: L.Scene, origins: Tensor, directions: Tensor, camera_indices: Optional[Tensor],
+                   starts: Tensor, ends: Tensor, app_mode: int = L.APP_MEAN, sh_unit_dir: bool = True,
+                   want_positions: bool = False) -> Dict[str, Tensor]:
+    """``cn_field_eval_f16``: ``field_eval`` with fp16 matrix operands and fp32 sums -- the forward of the reference's
+    mixed-precision training class, whose roundings ``field_backward_general(..., matrix_precision=MATRIX_F16)``
+    recomputes.  Built for the ``fruit_nerf_method`` and ``_big`` / ``_huge`` field shapes (``field_eval_f16_supported``);
+    other shapes raise ``CropNerfHipError`` (``CN_ERR_UNSUPPORTED``)."""
+    lib = L.load()
+    R, S = starts.shape
+    dev = starts.device
+    out = {"density": torch.empty(R, S, device=dev), "rgb": torch.empty(R, S, 3, device=dev),
+           "semantics": torch.empty(R, S, device=dev)}
+    pos = torch.empty(R, S, 3, device=dev) if want_positions else None
+    L.check(lib.cn_field_eval_f16(C.byref(fh.struct), C.byref(scene), app_mode, 1 if sh_unit_dir else 0,
+                                  _p(_f32(origins, "origins")), _p(_f32(directions, "directions")),
+                                  _p(_i64(camera_indices, "camera_indices")), _p(_f32(starts, "starts")),
+                                  _p(_f32(ends, "ends")), R, S, _p(out["density"]), _p(out["rgb"]), _p(out["semantics"]),
+                                  _p(pos), _stream(starts)))
+    if pos is not None:
+        out["positions"] = pos
+    return out
+
+
+def field_eval_f16_supported(spec) -> bool:
+    """True for the field shapes ``cn_field_eval_f16`` is built for: 16 levels x 2 features, base 64 wide, appearance 32,
+    colour 64 wide, and either geo 15 with 2 x 64 semantic layers or geo 30 with 3 x 128."""
+    if not (spec.grid.num_levels == 16 and spec.grid.features_per_level == 2 and spec.hidden_dim == 64
+            and spec.appearance_embedding_dim == 32 and spec.hidden_dim_color == 64 and spec.num_layers_color == 3
+            and spec.hidden_dim_transient == 64):
+        return False
+    return ((spec.geo_feat_dim, spec.num_layers_semantic, spec.hidden_dim_semantics) in ((15, 2, 64), (30, 3, 128)))
+
+
 def composite(starts: Tensor, ends: Tensor, density: Tensor, rgb: Optional[Tensor] = None,
               semantics: Optional[Tensor] = None, bg_mode: int = L.BG_LAST_SAMPLE,
               bg_color: Sequence[float] = (0.0, 0.0, 0.0), eval_clamp: bool = True, want_weights: bool = False
@@ -884,21 +917,24 @@ def field_backward_general(fh: FieldHandle, gh: FieldHandle, scene: L.Scene, ori
                            d_rgb: Tensor, d_semantics: Tensor, app_mode: int = L.APP_PER_CAMERA,
                            sh_unit_dir: bool = True, app_mean: Optional[Tensor] = None,
                            workspace: Optional[Tensor] = None, d_positions: Optional[Tensor] = None,
-                           d_directions: Optional[Tensor] = None, flags: int = 0) -> Tensor:
+                           d_directions: Optional[Tensor] = None, flags: int = 0,
+                           matrix_precision: int = L.MATRIX_FP32) -> Tensor:
     """``cn_field_backward_general``: parameter gradients for any field shape of the reference's configs (accumulated
     into the tensors behind ``gh``).  Returns the workspace so the caller can reuse it.  ``flags`` as for
-    ``field_backward`` (``cn_field_backward_general_ex``)."""
+    ``field_backward``; ``matrix_precision``: ``MATRIX_F16`` = the reference's mixed-precision class (fp16 forward
+    recompute, the function ``field_eval_f16`` computes; bf16 gradient products; fp32 sums), ``MATRIX_FP32`` and
+    ``MATRIX_SPLIT_BF16`` = exact fp32 (``cn_field_backward_general_mp``)."""
     lib = L.load()
     R, S = starts.shape
     need = lib.cn_field_backward_general_workspace_bytes(C.byref(fh.struct))
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty(need, dtype=torch.uint8, device=starts.device)
-    L.check(lib.cn_field_backward_general_ex(
+    L.check(lib.cn_field_backward_general_mp(
         C.byref(fh.struct), C.byref(gh.struct), C.byref(scene), app_mode, 1 if sh_unit_dir else 0,
         _p(_f32(app_mean, "app_mean")), _p(_f32(origins, "origins")), _p(_f32(directions, "directions")),
         _p(_i64(camera_indices, "camera_indices")), _p(_f32(starts, "starts")), _p(_f32(ends, "ends")),
         _p(_f32(d_density, "d_density")), _p(_f32(d_rgb, "d_rgb")), _p(_f32(d_semantics, "d_semantics")), R, S,
-        _p(_f32(d_positions, "d_positions")), _p(_f32(d_directions, "d_directions")), int(flags),
+        _p(_f32(d_positions, "d_positions")), _p(_f32(d_directions, "d_directions")), int(flags), int(matrix_precision),
         C.c_void_p(workspace.data_ptr()), workspace.numel(), _stream(starts)))
     return workspace
 

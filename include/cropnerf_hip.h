@@ -384,12 +384,22 @@ int cn_field_eval(const cn_field_params* params, const cn_scene* scene, int32_t 
  * chooses it for the fused renderers: CN_MATRIX_SPLIT_BF16 evaluates the two field shapes of the reference's method configs
  * (fruit_nerf_method and fruit_nerf_method_big / _huge, fruit_nerf/fruit_nerf_config.py:29-172) with every matrix operand as
  * bf16 hi + lo and fp32 accumulation -- the path the _big / _huge models render and export through; CN_MATRIX_F16 takes the same
- * kernel (there is no fp16-operand form of the shape-generic evaluation); any other shape is evaluated in exact fp32. */
+ * kernel (the fp16-operand form of these two shapes is the separate entry cn_field_eval_f16, below); any other shape is
+ * evaluated in exact fp32. */
 int cn_field_eval_mp(const cn_field_params* params, const cn_scene* scene, int32_t app_mode, int32_t sh_unit_dir,
                      const float* origins, const float* directions, const int64_t* camera_indices,
                      const float* starts, const float* ends, int64_t num_rays, int32_t num_samples,
                      float* density, float* rgb, float* semantics, float* positions, int32_t matrix_precision,
                      cn_stream_t stream);
+/* The same in true fp16 matrix arithmetic -- the forward of the reference's mixed-precision training class for the two field
+ * shapes of its method configs (fruit_nerf_method: geo 15, 2 x 64 semantic layers; fruit_nerf_method_big / _huge: geo 30,
+ * 3 x 128): weights and every layer input (the interpolated feature included) rounded to fp16 (nearest even), fp32
+ * accumulation, density / rgb / semantics from the fp32 sums.  These are the roundings cn_field_backward_general_mp
+ * recomputes under CN_MATRIX_F16, so the ReLU gates of the two agree.  Other shapes: CN_ERR_UNSUPPORTED. */
+int cn_field_eval_f16(const cn_field_params* params, const cn_scene* scene, int32_t app_mode, int32_t sh_unit_dir,
+                      const float* origins, const float* directions, const int64_t* camera_indices,
+                      const float* starts, const float* ends, int64_t num_rays, int32_t num_samples,
+                      float* density, float* rgb, float* semantics, float* positions, cn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Compositing
@@ -636,6 +646,19 @@ int cn_field_backward_general_ex(const cn_field_params* params, const cn_field_p
                                  const float* d_semantics, int64_t num_rays, int32_t num_samples, float* d_positions,
                                  float* d_directions, uint32_t flags, void* workspace, size_t workspace_bytes,
                                  cn_stream_t stream);
+/* The same with the matrix arithmetic of the caller's choice (cn_field_backward_general_ex = CN_MATRIX_FP32), as for
+ * cn_field_backward_mp.  CN_MATRIX_F16: the reference's mixed-precision class -- the forward recompute with fp16 operands
+ * (weights and layer inputs rounded to nearest even, table values read unrounded, the interpolated feature rounded once:
+ * the function cn_field_eval_f16 computes), the gradient products dX and dW with bf16 operands, fp32 accumulation
+ * throughout, fp32 master gradients out.  CN_MATRIX_SPLIT_BF16 (a ~fp32 forward) and CN_MATRIX_FP32: the exact-fp32
+ * kernel.  Any other value: CN_ERR_INVALID. */
+int cn_field_backward_general_mp(const cn_field_params* params, const cn_field_params* grads, const cn_scene* scene,
+                                 int32_t app_mode, int32_t sh_unit_dir, const float* app_mean, const float* origins,
+                                 const float* directions, const int64_t* camera_indices, const float* starts,
+                                 const float* ends, const float* d_density, const float* d_rgb,
+                                 const float* d_semantics, int64_t num_rays, int32_t num_samples, float* d_positions,
+                                 float* d_directions, uint32_t flags, int32_t matrix_precision, void* workspace,
+                                 size_t workspace_bytes, cn_stream_t stream);
 
 /* Parameter gradients of one proposal network from d loss / d density [R,S]; d_positions as above. */
 int cn_proposal_backward(const cn_density_params* params, const cn_density_params* grads, const cn_scene* scene,

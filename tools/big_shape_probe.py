@@ -1,6 +1,8 @@
 """Throughput of the shape-generic path on the fruit_nerf_method_big field (geo 30, 3 x 128 semantic layers, 2^21-entry
-levels, 128 samples per ray behind a (512, 256) proposal sampler).  Profiling aid:  python tools/big_shape_probe.py"""
-import json, os, sys, time, torch
+levels, 128 samples per ray behind a (512, 256) proposal sampler).  Profiling aid:  python tools/big_shape_probe.py
+(METHOD = another method specification, PROBE = render | train | both, TRAIN_RAYS, TRAIN_MATRIX = fp32 | f16: the training
+iteration's matrix arithmetic, "f16" = the mixed-precision class)"""
+import dataclasses, json, os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cropnerf_amd import synthetic
 from cropnerf_amd.fruit_nerf.fruit_nerf import FruitModel, Semantics
@@ -8,6 +10,8 @@ from cropnerf_amd.fruit_nerf import fruit_nerf_config as FC
 from cropnerf_amd.rays import Cameras, SceneBox
 
 cfg = getattr(FC, os.environ.get("METHOD", "fruit_nerf_method_big")).config.pipeline.model
+if "TRAIN_MATRIX" in os.environ:
+    cfg = dataclasses.replace(cfg, matrix_precision=os.environ["TRAIN_MATRIX"])
 c2w, intr = synthetic.orbit_cameras(8, height=800, width=800)
 cams = Cameras(c2w, intr[:, 0], intr[:, 1], intr[:, 2], intr[:, 3], 800, 800).to("cuda")
 m = FruitModel(cfg, SceneBox(torch.tensor(synthetic.SCENE_AABB)), 8, {"semantics": Semantics()}, device="cuda", test_mode="inference")
@@ -51,4 +55,5 @@ for _ in range(5):
     tr.train_iteration(rays, batch)
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t) / 5
-print(json.dumps({"train_rays": Rt, "ms_per_iter": round(dt * 1e3, 2), "rays_per_sec": Rt / dt}))
+print(json.dumps({"train_rays": Rt, "train_matrix_precision": m.train_matrix_precision(), "ms_per_iter": round(dt * 1e3, 2),
+                  "rays_per_sec": Rt / dt}))
