@@ -211,6 +211,9 @@ SIGNATURES = {
     "cn_deterministic_register": (C.c_int, [_P, _I64, _P, _P]),
     "cn_deterministic_clear": (C.c_int, []),
     "cn_deterministic_flush": (C.c_int, [_P]),
+    "cn_uncertainty_table": (C.c_int, [_P, _I32, C.c_double, _P, _P]),
+    "cn_uncertainty_lookup": (C.c_int, [_P, _P, _P, _P, _I64, _I32, C.POINTER(Scene), _P, _I32, _P, _P, _F, _P]),
+    "cn_uncertainty_composite": (C.c_int, [_P, _P, _I64, _I32, _P, _P]),
 }
 
 DET_LIB_PATH = _HERE / "libcropnerf_hip_det.so"

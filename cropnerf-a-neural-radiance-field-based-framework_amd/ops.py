@@ -672,6 +672,57 @@ def composite(starts: Tensor, ends: Tensor, density: Tensor, rgb: Optional[Tenso
     return out
 
 
+def uncertainty_lod(num_vertices: int) -> int:
+    """``lod`` of a Hessian grid of ``(2^lod + 1)^3`` values (``bayesrays/run_viewer_u.py:377``); ``ValueError`` otherwise."""
+    for lod in range(1, 11):
+        if ((1 << lod) + 1) ** 3 == num_vertices:
+            return lod
+    raise ValueError(f"{num_vertices} values are not a (2^k + 1)^3 grid with 1 <= k <= 10")
+
+
+def uncertainty_table(hessian: Tensor, N: float, lod: Optional[int] = None) -> Tensor:
+    """``cn_uncertainty_table``: ``1 / (hessian / N + 1e-4 / (2^lod)^3)`` (``bayesrays/output_uncertainty.py:36-39``)."""
+    lib = L.load()
+    hessian = _f32(hessian, "hessian")
+    if lod is None:
+        lod = uncertainty_lod(hessian.numel())
+    elif hessian.numel() != ((1 << lod) + 1) ** 3:
+        raise ValueError(f"hessian has {hessian.numel()} values, lod {lod} needs {((1 << lod) + 1) ** 3}")
+    un = torch.empty_like(hessian)
+    L.check(lib.cn_uncertainty_table(_p(hessian), int(lod), float(N), _p(un), _stream(hessian)))
+    return un
+
+
+def uncertainty_lookup(origins: Tensor, directions: Tensor, starts: Tensor, ends: Tensor, scene: L.Scene, un: Tensor,
+                       lod: int, density: Optional[Tensor] = None, filter_value: float = 0.0) -> Tensor:
+    """``cn_uncertainty_lookup``: per-sample log10 uncertainty [R,S] (``get_uncertainty``, ``output_uncertainty.py:19-30``).
+    With ``density`` [R,S]: ``density *= (un_points <= filter_value)`` in place (``:46, :60``)."""
+    lib = L.load()
+    R, S = starts.shape
+    if _f32(un, "un").numel() != ((1 << lod) + 1) ** 3:  # every corner index is below (2^lod + 1)^3
+        raise ValueError(f"un has {un.numel()} values, lod {lod} needs {((1 << lod) + 1) ** 3}")
+    if density is not None and tuple(density.shape) != (R, S):
+        raise ValueError(f"density shape {tuple(density.shape)} != {(R, S)}")
+    out = torch.empty(R, S, device=starts.device)
+    L.check(lib.cn_uncertainty_lookup(_p(_f32(origins, "origins")), _p(_f32(directions, "directions")),
+                                      _p(_f32(starts, "starts")), _p(_f32(ends, "ends")), R, S, C.byref(scene), _p(un),
+                                      int(lod), _p(out), _p(_f32(density, "density")), float(filter_value),
+                                      _stream(starts)))
+    return out
+
+
+def uncertainty_composite(weights: Tensor, un_points: Tensor) -> Tensor:
+    """``cn_uncertainty_composite``: the ``uncertainty`` image [R,1] in [0, 1] (``output_uncertainty.py:65-70``)."""
+    lib = L.load()
+    R, S = weights.shape
+    if tuple(un_points.shape) != (R, S):
+        raise ValueError(f"un_points shape {tuple(un_points.shape)} != {(R, S)}")
+    out = torch.empty(R, 1, device=weights.device)
+    L.check(lib.cn_uncertainty_composite(_p(_f32(weights, "weights")), _p(_f32(un_points, "un_points")), R, S, _p(out),
+                                         _stream(weights)))
+    return out
+
+
 def render_rays(fh: FieldHandle, scene: L.Scene, opts: L.RenderOpts, origins: Tensor, directions: Tensor,
                 nears: Tensor, fars: Tensor, camera_indices: Optional[Tensor] = None, bins: Optional[Tensor] = None,
                 want_weights: bool = False) -> Dict[str, Tensor]:

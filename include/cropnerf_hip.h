@@ -871,6 +871,35 @@ int cn_deterministic_register(float* base, int64_t count, int64_t* shadow, uint6
 int cn_deterministic_clear(void);
 int cn_deterministic_flush(cn_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * BayesRays, consumer side (fruit_nerf/bayesrays/output_uncertainty.py, bayesrays/utils.py, bayesrays/run_viewer_u.py):
+ * from a Hessian grid of (2^lod + 1)^3 floats -- the `unc.npy` that bayesrays/uncertainty.py writes -- to a per-sample log
+ * uncertainty, an optional density mask and the composited `uncertainty` image.  The Hessian stage itself is not built.
+ *
+ * cn_uncertainty_table (output_uncertainty.py:36-39), once per model:
+ *   un[i] = 1 / (hessian[i] / N + 1e-4 / (2^lod)^3),  i < (2^lod + 1)^3.
+ *
+ * cn_uncertainty_lookup (get_uncertainty :19-30 on find_grid_indices(..., zero_out=False) and normalize_point_coords,
+ * utils.py:6-41), one value per sample: position = origin + direction * (start + end) / 2, normalised for `scene` exactly as
+ * the field kernels normalise it (L-inf contraction and (p + 2) / 4, or the box; zeroed outside (0, 1)^3), coords = pos * L
+ * with L = 2^lod; the eight corners (cx, cy, cz) in {0, 1}^3 LITERALLY as the reference indexes them --
+ *   index = (floor(x) + cx) * L^2 + (floor(y) + cy) * L + (floor(z) + cz)      (stride L, not L + 1: vertices alias),
+ *   coef  = |x - (floor(x) + 1 - cx)| * |y - ...| * |z - ...|,   weight = coef^2 / sum of the eight coef^2,
+ *   un_points = log10(sqrt(sum un[index] * weight) + 1e-12).
+ * The largest index, L^3 + L^2 + L, lies inside the (L + 1)^3 table; 1 <= lod <= 10 is checked on the host.
+ * `density` ([R,S], may be NULL): density *= (un_points <= filter_value) in place (:46, :60; the caller passes
+ * filter_thresh * 6).
+ *
+ * cn_uncertainty_composite (:65-70): u = sum_s w * un_points + (1 - sum_s w) * (-3), clipped to [-3, 6], (u + 3) / 9.
+ * uncertainty [R,1].
+ * ------------------------------------------------------------------------------------------- */
+int cn_uncertainty_table(const float* hessian, int32_t lod, double N, float* un, cn_stream_t stream);
+int cn_uncertainty_lookup(const float* origins, const float* directions, const float* starts, const float* ends,
+                          int64_t num_rays, int32_t num_samples, const cn_scene* scene, const float* un, int32_t lod,
+                          float* un_points, float* density, float filter_value, cn_stream_t stream);
+int cn_uncertainty_composite(const float* weights, const float* un_points, int64_t num_rays, int32_t num_samples,
+                             float* uncertainty, cn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
