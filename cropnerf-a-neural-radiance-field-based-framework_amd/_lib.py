@@ -214,6 +214,10 @@ SIGNATURES = {
     "cn_uncertainty_table": (C.c_int, [_P, _I32, C.c_double, _P, _P]),
     "cn_uncertainty_lookup": (C.c_int, [_P, _P, _P, _P, _I64, _I32, C.POINTER(Scene), _P, _I32, _P, _P, _F, _P]),
     "cn_uncertainty_composite": (C.c_int, [_P, _P, _I64, _I32, _P, _P]),
+    "cn_semantics_density_gradient": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _P, _P, _P]),
+    "cn_field_density_position_gradient": (C.c_int, [C.POINTER(FieldParams), C.POINTER(Scene), _P, _P, _P, _P, _P, _I64,
+                                                     _I32, _P, _P, _P]),
+    "cn_hessian_accumulate": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, C.POINTER(Scene), _I32, _F, _P, _P]),
 }
 
 DET_LIB_PATH = _HERE / "libcropnerf_hip_det.so"

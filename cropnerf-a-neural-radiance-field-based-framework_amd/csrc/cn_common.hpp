@@ -214,6 +214,41 @@ __device__ __forceinline__ bool normalize_position(const SceneDev& sc, float& x,
   return sel;
 }
 
+// d(loss)/d(normalised position) -> d(loss)/d(world position): the transpose Jacobian of normalize_position
+// (L-inf scene contraction then (c+2)/4, or the AABB normalisation), zero where the selector dropped the sample.
+__device__ __forceinline__ void normalize_position_backward(const SceneDev& sc, float x, float y, float z, float sel,
+                                                            float& gx, float& gy, float& gz) {
+  if (sc.contraction) {
+    gx *= 0.25f * sel;
+    gy *= 0.25f * sel;
+    gz *= 0.25f * sel;
+    const float axv = fabsf(x), ayv = fabsf(y), azv = fabsf(z);
+    const float m = fmaxf(axv, fmaxf(ayv, azv));
+    if (m >= 1.f) {
+      const float inv = 1.f / m;
+      const float k = (2.f - inv) * inv;
+      const float s = gx * x + gy * y + gz * z;
+      const float coef = 2.f * inv * inv * (inv - 1.f) * s;  // d k / d m * <g, p>
+      gx *= k;
+      gy *= k;
+      gz *= k;
+      if (axv >= ayv && axv >= azv) gx += x < 0.f ? -coef : coef;
+      else if (ayv >= azv) gy += y < 0.f ? -coef : coef;
+      else gz += z < 0.f ? -coef : coef;
+    }
+  } else {
+    gx *= sc.inv_extent[0] * sel;
+    gy *= sc.inv_extent[1] * sel;
+    gz *= sc.inv_extent[2] * sel;
+  }
+}
+
+// Weights are read-only for the whole launch (gradients go to separate buffers), so they are addressed through the
+// constant address space: with a wave-uniform index the compiler then emits s_load (SGPR operands for v_fma) instead of
+// one broadcast global_load per multiply -- it cannot prove invariance for plain global pointers next to the atomics.
+typedef const float __attribute__((address_space(4)))* cfloat_ptr;
+__device__ __forceinline__ cfloat_ptr as_const(const float* p) { return (cfloat_ptr)(unsigned long long)p; }
+
 // One level of the hash grid: 8 corner gathers of two features + trilinear blend in the order of
 // HashEncoding.pytorch_fwd (x toward the upper corner, then y, then z).  tcnn's kernel_grid sums the same eight
 // weight * value products corner by corner; the results differ in fp32 rounding only.
@@ -301,18 +336,19 @@ __device__ __forceinline__ float2 hash_level(const void* __restrict__ table, con
 // partial blends the interpolation forms anyway.  The training backward takes the position gradient of a (sample, level) as
 // g0 * J.x + g1 * J.y from these six numbers instead of gathering the eight corners a second time once g is known.
 typedef float v2f_t __attribute__((ext_vector_type(2)));
+template <bool HALF = false>
 __device__ __forceinline__ float2 hash_level_jac(const void* __restrict__ table, const Lvl& lv, float pos_offset, float px, float py,
                                                  float pz, v2f_t& jx, v2f_t& jy, v2f_t& jz) {
   const Cell k = hash_cell(lv, pos_offset, px, py, pz);
   const float ox = k.ox, oy = k.oy, oz = k.oz;
-  float2 ccc = hash_gather<false>(table, ((k.hx1 ^ k.hy1 ^ k.hz1) & lv.mask) + lv.off);
-  float2 cfc = hash_gather<false>(table, ((k.hx1 ^ k.hy0 ^ k.hz1) & lv.mask) + lv.off);
-  float2 ffc = hash_gather<false>(table, ((k.hx0 ^ k.hy0 ^ k.hz1) & lv.mask) + lv.off);
-  float2 fcc = hash_gather<false>(table, ((k.hx0 ^ k.hy1 ^ k.hz1) & lv.mask) + lv.off);
-  float2 ccf = hash_gather<false>(table, ((k.hx1 ^ k.hy1 ^ k.hz0) & lv.mask) + lv.off);
-  float2 cff = hash_gather<false>(table, ((k.hx1 ^ k.hy0 ^ k.hz0) & lv.mask) + lv.off);
-  float2 fff = hash_gather<false>(table, ((k.hx0 ^ k.hy0 ^ k.hz0) & lv.mask) + lv.off);
-  float2 fcf = hash_gather<false>(table, ((k.hx0 ^ k.hy1 ^ k.hz0) & lv.mask) + lv.off);
+  float2 ccc = hash_gather<HALF>(table, ((k.hx1 ^ k.hy1 ^ k.hz1) & lv.mask) + lv.off);
+  float2 cfc = hash_gather<HALF>(table, ((k.hx1 ^ k.hy0 ^ k.hz1) & lv.mask) + lv.off);
+  float2 ffc = hash_gather<HALF>(table, ((k.hx0 ^ k.hy0 ^ k.hz1) & lv.mask) + lv.off);
+  float2 fcc = hash_gather<HALF>(table, ((k.hx0 ^ k.hy1 ^ k.hz1) & lv.mask) + lv.off);
+  float2 ccf = hash_gather<HALF>(table, ((k.hx1 ^ k.hy1 ^ k.hz0) & lv.mask) + lv.off);
+  float2 cff = hash_gather<HALF>(table, ((k.hx1 ^ k.hy0 ^ k.hz0) & lv.mask) + lv.off);
+  float2 fff = hash_gather<HALF>(table, ((k.hx0 ^ k.hy0 ^ k.hz0) & lv.mask) + lv.off);
+  float2 fcf = hash_gather<HALF>(table, ((k.hx0 ^ k.hy1 ^ k.hz0) & lv.mask) + lv.off);
   const float mx = 1.f - ox, my = 1.f - oy, mz = 1.f - oz;
   auto V = [](float2 t) {
     v2f_t v;

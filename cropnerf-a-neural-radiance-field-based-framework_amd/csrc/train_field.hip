@@ -33,12 +33,6 @@ constexpr int TS = 64;       // samples per tile
 constexpr int LD = TS + 1;   // padded row length
 constexpr int TB = 256;      // threads per workgroup
 
-// Weights are read-only for the whole launch (gradients go to separate buffers), so they are addressed through the
-// constant address space: with a wave-uniform index the compiler then emits s_load (SGPR operands for v_fma) instead of
-// one broadcast global_load per multiply -- it cannot prove invariance for plain global pointers next to the atomics.
-typedef const float __attribute__((address_space(4)))* cfloat_ptr;
-__device__ __forceinline__ cfloat_ptr as_const(const float* p) { return (cfloat_ptr)(unsigned long long)p; }
-
 // y[n][lane] = act(b[n] + sum_k W[n][k] x[k][lane]) for the rows n = wave, wave+4, ...
 template <int K, int N, bool RELU>
 __device__ __forceinline__ void fwd_rows(const float* __restrict__ Wg, const float* __restrict__ bg, const float* x,
@@ -597,35 +591,6 @@ inline void launch_coarse_reduce(const CoarseScatter& c, const GridDev& grid, fl
   if (!c.base) return;
   const unsigned nv = c.n1 * c.n1 * c.n1;
   hipLaunchKernelGGL(coarse_scatter_reduce_kernel, dim3((nv + 63) / 64), dim3(256), 0, stream, c, grid.level(0), gtab);
-}
-
-// d(loss)/d(normalised position) -> d(loss)/d(world position): the transpose Jacobian of normalize_position
-// (L-inf scene contraction then (c+2)/4, or the AABB normalisation), zero where the selector dropped the sample.
-__device__ __forceinline__ void normalize_position_backward(const SceneDev& sc, float x, float y, float z, float sel,
-                                                            float& gx, float& gy, float& gz) {
-  if (sc.contraction) {
-    gx *= 0.25f * sel;
-    gy *= 0.25f * sel;
-    gz *= 0.25f * sel;
-    const float axv = fabsf(x), ayv = fabsf(y), azv = fabsf(z);
-    const float m = fmaxf(axv, fmaxf(ayv, azv));
-    if (m >= 1.f) {
-      const float inv = 1.f / m;
-      const float k = (2.f - inv) * inv;
-      const float s = gx * x + gy * y + gz * z;
-      const float coef = 2.f * inv * inv * (inv - 1.f) * s;  // d k / d m * <g, p>
-      gx *= k;
-      gy *= k;
-      gz *= k;
-      if (axv >= ayv && axv >= azv) gx += x < 0.f ? -coef : coef;
-      else if (ayv >= azv) gy += y < 0.f ? -coef : coef;
-      else gz += z < 0.f ? -coef : coef;
-    }
-  } else {
-    gx *= sc.inv_extent[0] * sel;
-    gy *= sc.inv_extent[1] * sel;
-    gz *= sc.inv_extent[2] * sel;
-  }
 }
 
 // d SH_deg4 / d (x, y, z) contracted with g[16] (the derivative of sh_deg4 in cn_common.hpp, term by term)

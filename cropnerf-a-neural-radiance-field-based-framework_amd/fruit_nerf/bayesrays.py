@@ -1,8 +1,16 @@
-"""BayesRays, consumer side -- mirror of ``crop_nerf/fruit_nerf/bayesrays/output_uncertainty.py`` (``get_uncertainty :19-30``,
-``get_output_nerfacto_new :32-111``, ``get_output_nerfacto_all :279-314``) and of the attributes ``bayesrays/run_viewer_u.py``
-sets on the model (``:373-382``; its ``get_output_nerfacto_new :80-170`` adds the semantic outputs).
+"""BayesRays -- mirror of ``crop_nerf/fruit_nerf/bayesrays``: the Hessian stage (``uncertainty.py``) and the renders made from
+its grid (``output_uncertainty.py``: ``get_uncertainty :19-30``, ``get_output_nerfacto_new :32-111``,
+``get_output_nerfacto_all :279-314``, with the attributes ``run_viewer_u.py`` sets on the model, ``:373-382``; its
+``get_output_nerfacto_new :80-170`` adds the semantic outputs).
 
-From a Hessian grid -- the ``unc.npy`` that ``bayesrays/uncertainty.py`` writes; that stage is not built here -- to an
+Producer: ``compute_hessian`` walks training batches with the model in eval (no jitter, eval near plane, eval appearance
+embedding, no camera-optimizer step), takes the proposal sampler's final samples and accumulates, per ray and literal grid vertex,
+``3 |sum coef * d semantics / d x|^2`` (``uncertainty.py:44-90, 292-339``): ``cn_field_eval`` -> ``cn_semantics_density_gradient``
+-> ``cn_field_density_position_gradient`` -> ``cn_hessian_accumulate``.  The rendered semantics reach the sample positions through
+the density only -- the logits come from detached geo features (``fruit_field.py:264-266``) -- so ``pass_semantic_gradients=True``
+is refused rather than computed in the detached form.  The field runs in fp32 here whatever the model's ``matrix_precision``.
+
+Consumer: from a Hessian grid -- the ``unc.npy`` of the producer or of the reference's script -- to an
 ``uncertainty`` image and, with ``filter_out``, renders from which uncertain matter is removed: the mask
 ``un_points <= filter_thresh * 6`` multiplies every density, in the proposal networks and in the field, before its weights.
 
@@ -17,7 +25,7 @@ from __future__ import annotations
 
 import os
 from dataclasses import dataclass, field
-from typing import Dict, Optional, Sequence
+from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -28,7 +36,8 @@ from .. import ops
 from ..rays import RayBundle
 
 __all__ = ["MAX_UNCERTAINTY", "MIN_UNCERTAINTY", "DEFAULT_N", "load_hessian", "UncertaintyState",
-           "get_outputs_with_uncertainty", "get_outputs_for_filter_levels"]
+           "get_outputs_with_uncertainty", "get_outputs_for_filter_levels", "hessian_for_samples", "hessian_for_rays",
+           "compute_hessian"]
 
 MAX_UNCERTAINTY, MIN_UNCERTAINTY = 6, -3  # output_uncertainty.py:41-42 (cn_uncertainty_composite holds the same two)
 DEFAULT_N = 1000 * 4096  # run_viewer_u.py:376: query iterations x rays per batch of the Hessian stage
@@ -38,7 +47,7 @@ def load_hessian(path, lod: Optional[int] = None):
     """``unc.npy`` -> (float32 array [(2^lod + 1)^3], lod).  ``lod`` is inferred from the length (``run_viewer_u.py:377``);
     ``ValueError`` when the length is not ``(2^k + 1)^3`` (or not the given ``lod``'s)."""
     if not os.path.exists(path):
-        raise FileNotFoundError(f"{path}: no Hessian file (the unc.npy that bayesrays/uncertainty.py writes)")
+        raise FileNotFoundError(f"{path}: no Hessian file (the unc.npy that `uncertainty.py compute` writes)")
     h = np.ascontiguousarray(np.load(str(path)), dtype=np.float32).reshape(-1)
     inferred = ops.uncertainty_lod(h.size)
     if lod is not None and int(lod) != inferred:
@@ -155,3 +164,71 @@ def get_outputs_for_filter_levels(model, ray_bundle: RayBundle, state: Uncertain
         for k in ("rgb", "accumulation", "depth"):
             outputs[f"{k}-{thresh:.2f}"] = res[k]
     return outputs
+
+
+# ------------------------------------------------------------------------------------------------ the Hessian stage
+def _refuse_semantic_gradients(model) -> None:
+    if getattr(model.config, "pass_semantic_gradients", False):
+        raise NotImplementedError(
+            "pass_semantic_gradients=True: the semantic logits then depend on the sample positions as well, and the Hessian "
+            "stage differentiates the density path only (the reference's default, detached geo features)")
+
+
+def _new_hessian(lod: int, device) -> Tensor:
+    if not 1 <= int(lod) <= 10:
+        raise ValueError(f"lod {lod} outside [1, 10]")
+    return torch.zeros(((1 << int(lod)) + 1) ** 3, dtype=torch.float32, device=device)
+
+
+@torch.no_grad()
+def hessian_for_samples(model, origins: Tensor, directions: Tensor, camera_indices: Optional[Tensor], starts: Tensor,
+                        ends: Tensor, lod: int, out: Optional[Tensor] = None) -> Tensor:
+    """One batch of ``find_uncertainty`` (``uncertainty.py:44-90``) on given samples: adds to ``out`` (a new zero grid of
+    ``(2^lod + 1)^3`` floats when None) and returns it."""
+    _refuse_semantic_gradients(model)
+    if out is None:
+        out = _new_hessian(lod, starts.device)
+    scene = model._scene(model._field_contraction)
+    fo = ops.field_eval(model.field, scene, origins, directions, camera_indices, starts, ends, app_mode=model._app_mode(),
+                        sh_unit_dir=model.config.sh_input == "unit", matrix_precision=L.MATRIX_FP32)
+    dd = ops.semantics_density_gradient(starts, ends, fo["density"], fo["semantics"])["d_density"]
+    dp = ops.field_density_position_gradient(model.field, scene, origins, directions, starts, ends, dd)["d_positions"]
+    return ops.hessian_accumulate(origins, directions, starts, ends, dp, scene, lod, out)  # 3: semantics.repeat(1, 3), :326
+
+
+@torch.no_grad()
+def hessian_for_rays(model, ray_bundle: RayBundle, lod: int, out: Optional[Tensor] = None) -> Tensor:
+    """``get_unc_nerfacto`` + ``find_uncertainty`` for one ray bundle: collider, the model's proposal sampler as it runs in the
+    model's current mode (``compute_hessian`` puts it in eval), then ``hessian_for_samples`` on its final samples."""
+    _refuse_semantic_gradients(model)
+    cfg = model.config
+    rb = model._prepared(ray_bundle)
+    cam = model._cam_idx(rb)
+    if model._app_mode() == L.APP_PER_CAMERA and cam is None:
+        raise AttributeError("Camera indices are not provided.")
+    ps = ops.proposal_sample(model.proposal_networks, model._scene(model._prop_contraction), rb.origins, rb.directions,
+                             rb.nears, rb.fars, cfg.num_proposal_samples_per_ray, cfg.num_nerf_samples_per_ray,
+                             anneal=model._anneal, matrix_precision=L.MATRIX_FP32)
+    bins = ps["euclidean_bins"]
+    return hessian_for_samples(model, rb.origins, rb.directions, cam, bins[:, :-1].contiguous(), bins[:, 1:].contiguous(),
+                               lod, out)
+
+
+def compute_hessian(model, datamanager, lod: int = 8, iters: int = 1000) -> Tuple[np.ndarray, int]:
+    """``ComputeUncertainty.main`` (``uncertainty.py:292-339``): ``max(len(train_dataset), iters)`` batches of
+    ``datamanager.next_train`` through the model in eval.  Returns the float32 grid [(2^lod + 1)^3] -- what ``np.save`` writes
+    as ``unc.npy`` -- and N = batches x rays per batch, the count ``UncertaintyState`` divides by."""
+    _refuse_semantic_gradients(model)
+    hessian = _new_hessian(lod, model.device)
+    steps = max(len(datamanager.train_dataset), int(iters))
+    was_training = model.training
+    model.eval()
+    rays = 0
+    try:
+        for step in range(steps):
+            ray_bundle, _ = datamanager.next_train(step)
+            rays += int(ray_bundle.origins.reshape(-1, 3).shape[0])
+            hessian_for_rays(model, ray_bundle, lod, hessian)
+    finally:
+        model.training = was_training
+    return hessian.cpu().numpy(), rays

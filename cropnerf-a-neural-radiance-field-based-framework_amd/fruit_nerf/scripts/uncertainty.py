@@ -1,13 +1,21 @@
 #!/usr/bin/env python
-"""``uncertainty.py render`` -- BayesRays uncertainty and filtered views of a trained run from a Hessian grid (the consumer side
-of ``crop_nerf/fruit_nerf/bayesrays``: ``output_uncertainty.py`` as ``run_viewer_u.py:357-382`` sets it up; argparse instead of
-tyro, an image per eval camera instead of the viewer).
+"""BayesRays for a trained run (``crop_nerf/fruit_nerf/bayesrays``; argparse instead of tyro).
+
+``uncertainty.py compute`` -- the Hessian grid (``bayesrays/uncertainty.py``, the same field names):
+
+    python uncertainty.py compute --load-config RUN/config.json [--output-path unc.npy] [--lod 8] [--iters 1000]
+
+Writes ``(2^lod + 1)^3`` float32 values with ``np.save`` and prints N (batches x rays per batch: what ``render --N`` takes)
+and the elapsed time.
+
+``uncertainty.py render`` -- uncertainty and filtered views from such a grid (``output_uncertainty.py`` as
+``run_viewer_u.py:357-382`` sets it up; an image per eval camera instead of the viewer):
 
     python uncertainty.py render --load-config RUN/config.json --unc-path unc.npy --output-dir OUT \
         [--filter-out] [--filter-thresh 0.5] [--white-bg | --black-bg] [--num-rays 32768] [--N 4096000]
 
 Writes ``OUT/<stem>_uncertainty.png`` and ``OUT/<stem>_rgb.png`` per eval camera (the training cameras when the run holds no
-eval split).  ``unc.npy`` is what the reference's ``bayesrays/uncertainty.py`` saves: ``(2^lod + 1)^3`` Hessian values.
+eval split).
 """
 
 from __future__ import annotations
@@ -15,10 +23,39 @@ from __future__ import annotations
 import argparse
 import os
 import sys
+import time
 from dataclasses import dataclass
 from pathlib import Path
 
+import numpy as np
 import torch
+
+
+@dataclass
+class ComputeUncertainty:
+    """Fields as ``bayesrays/uncertainty.py:33-42``."""
+
+    load_config: Path
+    output_path: Path = Path("unc.npy")
+    lod: int = 8
+    iters: int = 1000
+
+    def main(self) -> None:
+        from cropnerf_amd.fruit_nerf import bayesrays as B
+        from cropnerf_amd.fruit_nerf.checkpoint import eval_setup
+
+        if not 1 <= self.lod <= 10:
+            raise SystemExit("--lod must lie in [1, 10]")
+        _, pipeline, _, _ = eval_setup(self.load_config, test_mode="test")
+        self.output_path.parent.mkdir(parents=True, exist_ok=True)
+        start = time.time()
+        hessian, n = B.compute_hessian(pipeline.model, pipeline.datamanager, self.lod, self.iters)
+        elapsed = time.time() - start
+        with open(str(self.output_path), "wb") as f:
+            np.save(f, hessian)
+        print(f"Saved {hessian.size} Hessian values (lod {self.lod}) to {self.output_path}")
+        print(f"N = {n} rays")
+        print(f"Execution time: {elapsed:.6f} seconds")
 
 
 @dataclass
@@ -71,6 +108,11 @@ class RenderUncertainty:
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     sub = ap.add_subparsers(dest="cmd", required=True)
+    c = sub.add_parser("compute")
+    c.add_argument("--load-config", type=Path, required=True)
+    c.add_argument("--output-path", type=Path, default=Path("unc.npy"))
+    c.add_argument("--lod", type=int, default=8)
+    c.add_argument("--iters", type=int, default=1000)
     r = sub.add_parser("render")
     r.add_argument("--load-config", type=Path, required=True)
     r.add_argument("--unc-path", type=Path, required=True)
@@ -87,6 +129,9 @@ def build_parser() -> argparse.ArgumentParser:
 
 def entrypoint(argv=None):
     a = build_parser().parse_args(argv)
+    if a.cmd == "compute":
+        ComputeUncertainty(a.load_config, a.output_path, a.lod, a.iters).main()
+        return
     if a.num_rays <= 0:
         raise SystemExit("--num-rays must be positive")
     RenderUncertainty(a.load_config, a.unc_path, a.output_dir, a.filter_out, a.filter_thresh, a.white_bg, a.black_bg,

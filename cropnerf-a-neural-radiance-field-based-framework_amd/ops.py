@@ -723,6 +723,61 @@ def uncertainty_composite(weights: Tensor, un_points: Tensor) -> Tensor:
     return out
 
 
+def semantics_density_gradient(starts: Tensor, ends: Tensor, density: Tensor, semantics: Tensor,
+                               want_weights: bool = False) -> Dict[str, Tensor]:
+    """``cn_semantics_density_gradient``: the rendered ``semantics`` [R,1] = sum_s w_s semantics_s and its derivative by every
+    density, ``d_density`` [R,S] (``bayesrays/uncertainty.py:326`` differentiates this scalar; the logits carry no gradient)."""
+    lib = L.load()
+    R, S = starts.shape
+    for t, nm in ((ends, "ends"), (density, "density"), (semantics, "semantics")):
+        if tuple(t.shape) != (R, S):
+            raise ValueError(f"{nm} shape {tuple(t.shape)} != {(R, S)}")
+    dev = starts.device
+    out = {"semantics": torch.empty(R, 1, device=dev), "d_density": torch.empty(R, S, device=dev)}
+    if want_weights:
+        out["weights"] = torch.empty(R, S, device=dev)
+    L.check(lib.cn_semantics_density_gradient(_p(_f32(starts, "starts")), _p(_f32(ends, "ends")), _p(_f32(density, "density")),
+                                              _p(_f32(semantics, "semantics")), R, S, _p(out["semantics"]),
+                                              _p(out.get("weights")), _p(out["d_density"]), _stream(starts)))
+    return out
+
+
+def field_density_position_gradient(fh: FieldHandle, scene: L.Scene, origins: Tensor, directions: Tensor, starts: Tensor,
+                                    ends: Tensor, d_density: Tensor, want_density: bool = False) -> Dict[str, Tensor]:
+    """``cn_field_density_position_gradient``: ``d_positions`` [R,S,3] = ``d_density`` * d sigma / d x in world coordinates
+    (fp32 arithmetic; no parameter gradient).  ``want_density``: also the density [R,S] it recomputed."""
+    lib = L.load()
+    R, S = starts.shape
+    if tuple(d_density.shape) != (R, S):
+        raise ValueError(f"d_density shape {tuple(d_density.shape)} != {(R, S)}")
+    dev = starts.device
+    out = {"d_positions": torch.empty(R, S, 3, device=dev)}
+    if want_density:
+        out["density"] = torch.empty(R, S, device=dev)
+    L.check(lib.cn_field_density_position_gradient(
+        C.byref(fh.struct), C.byref(scene), _p(_f32(origins, "origins")), _p(_f32(directions, "directions")),
+        _p(_f32(starts, "starts")), _p(_f32(ends, "ends")), _p(_f32(d_density, "d_density")), R, S, _p(out["d_positions"]),
+        _p(out.get("density")), _stream(starts)))
+    return out
+
+
+def hessian_accumulate(origins: Tensor, directions: Tensor, starts: Tensor, ends: Tensor, d_positions: Tensor,
+                       scene: L.Scene, lod: int, hessian: Tensor, channel_scale: float = 3.0) -> Tensor:
+    """``cn_hessian_accumulate``: adds this batch's ``channel_scale * |sum coef * g|^2`` per (ray, vertex) to ``hessian``
+    (``(2^lod + 1)^3`` floats, in place; returned).  ``channel_scale`` 3: ``bayesrays/uncertainty.py:326``."""
+    lib = L.load()
+    R, S = starts.shape
+    if tuple(d_positions.shape) != (R, S, 3):
+        raise ValueError(f"d_positions shape {tuple(d_positions.shape)} != {(R, S, 3)}")
+    if 1 <= int(lod) <= 10 and _f32(hessian, "hessian").numel() != ((1 << int(lod)) + 1) ** 3:  # every index is below it
+        raise ValueError(f"hessian has {hessian.numel()} values, lod {lod} needs {((1 << int(lod)) + 1) ** 3}")
+    L.check(lib.cn_hessian_accumulate(_p(_f32(origins, "origins")), _p(_f32(directions, "directions")),
+                                      _p(_f32(starts, "starts")), _p(_f32(ends, "ends")),
+                                      _p(_f32(d_positions, "d_positions")), R, S, C.byref(scene), int(lod),
+                                      float(channel_scale), _p(_f32(hessian, "hessian")), _stream(starts)))
+    return hessian
+
+
 def render_rays(fh: FieldHandle, scene: L.Scene, opts: L.RenderOpts, origins: Tensor, directions: Tensor,
                 nears: Tensor, fars: Tensor, camera_indices: Optional[Tensor] = None, bins: Optional[Tensor] = None,
                 want_weights: bool = False) -> Dict[str, Tensor]:

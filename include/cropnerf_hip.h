@@ -874,7 +874,7 @@ int cn_deterministic_flush(cn_stream_t stream);
 /* ---------------------------------------------------------------------------------------------
  * BayesRays, consumer side (fruit_nerf/bayesrays/output_uncertainty.py, bayesrays/utils.py, bayesrays/run_viewer_u.py):
  * from a Hessian grid of (2^lod + 1)^3 floats -- the `unc.npy` that bayesrays/uncertainty.py writes -- to a per-sample log
- * uncertainty, an optional density mask and the composited `uncertainty` image.  The Hessian stage itself is not built.
+ * uncertainty, an optional density mask and the composited `uncertainty` image.  (The grid's producer follows below.)
  *
  * cn_uncertainty_table (output_uncertainty.py:36-39), once per model:
  *   un[i] = 1 / (hessian[i] / N + 1e-4 / (2^lod)^3),  i < (2^lod + 1)^3.
@@ -899,6 +899,44 @@ int cn_uncertainty_lookup(const float* origins, const float* directions, const f
                           float* un_points, float* density, float filter_value, cn_stream_t stream);
 int cn_uncertainty_composite(const float* weights, const float* un_points, int64_t num_rays, int32_t num_samples,
                              float* uncertainty, cn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * BayesRays, producer side (bayesrays/uncertainty.py:44-90, 93-153, 292-339; bayesrays/utils.py:6-41): the Hessian grid.
+ * Per ray the reference renders semantics = sum_s w_s logit_s (weights NOT detached, logits from detached geo features --
+ * pass_semantic_gradients = False), differentiates it by a zero offset added to every sample position,
+ *   g_s = d semantics / d x_s = (d semantics / d sigma_s) * d sigma_s / d x_s,
+ * interpolates g_s onto the eight literal vertices of its cell, sums per (ray, vertex) and adds the squares:
+ *   H[index] += 3 * |sum_{(s, corner) of the ray with that index} coef * g_s|^2        (3: rgb = semantics.repeat(1, 3)).
+ *
+ * cn_semantics_density_gradient, one wavefront per ray, any num_samples:
+ *   w_s = nan_to_num((1 - exp(-delta_s sigma_s)) T_s) as cn_composite,  rendered_semantics[r] = sum_s w_s semantics_s,
+ *   d_density[r,s] = delta_s * (T_{s+1} semantics_s - sum_{j>s} w_j semantics_j).       weights [R,S] may be NULL.
+ *
+ * cn_field_density_position_gradient: d_positions[r,s,:] = d_density[r,s] * d sigma / d x in WORLD coordinates, with
+ *   sigma = trunc_exp(h_0) * selector (backward exp(clamp(h_0, -15, 15))), h = base MLP of the grid encoding, through the grid's
+ *   Jacobian and the Jacobian of the contraction / box normalisation -- the helpers cn_field_backward* use, so a sample is
+ *   selected and lands in a hash cell exactly as there.  It recomputes the gather and the first layer, back-propagates row 0 of
+ *   the second, writes no parameter gradient and issues no atomic.  density [R,S] (may be NULL) receives sigma.
+ *   ALWAYS fp32 arithmetic, whatever matrix_precision the model renders with.  Both grid layouts, both table dtypes.
+ *   Built for every field shape of the reference's methods: 16 grid levels, base MLP of 2 layers with width <= 128, any
+ *   geo_feat_dim; anything else: CN_ERR_UNSUPPORTED.
+ *
+ * cn_hessian_accumulate, one wavefront per ray: positions normalised and indexed exactly as cn_uncertainty_lookup does (one
+ *   device function serves both); coefficients are zero for deselected samples (zero_out=True).  The 8 * num_samples
+ *   contributions of a ray are merged by index in LDS before the square; hessian [(2^lod + 1)^3] is ADDED to with float
+ *   atomics (the caller zeroes it once).  channel_scale: 3 for the reference's call.  1 <= lod <= 10 and num_samples <= 256,
+ *   else CN_ERR_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------------- */
+int cn_semantics_density_gradient(const float* starts, const float* ends, const float* density, const float* semantics,
+                                  int64_t num_rays, int32_t num_samples, float* rendered_semantics, float* weights,
+                                  float* d_density, cn_stream_t stream);
+int cn_field_density_position_gradient(const cn_field_params* params, const cn_scene* scene, const float* origins,
+                                       const float* directions, const float* starts, const float* ends,
+                                       const float* d_density, int64_t num_rays, int32_t num_samples, float* d_positions,
+                                       float* density, cn_stream_t stream);
+int cn_hessian_accumulate(const float* origins, const float* directions, const float* starts, const float* ends,
+                          const float* d_positions, int64_t num_rays, int32_t num_samples, const cn_scene* scene, int32_t lod,
+                          float channel_scale, float* hessian, cn_stream_t stream);
 
 #ifdef __cplusplus
 }
