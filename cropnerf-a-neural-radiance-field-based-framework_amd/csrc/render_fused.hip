@@ -88,10 +88,14 @@ constexpr int MM_FP32 = CN_MATRIX_FP32, MM_BF16 = CN_MATRIX_SPLIT_BF16, MM_F16 =
 // Split-bf16 A operands (cn_render_opts.matrix_precision = 1).  Block b = one (row tile, K block of 32): [hi | lo][lane 64][8 bf16];
 // lane (g, j) holds row 16 mt + j and the eight k values its B operand lane supplies.  B operands are the features of a
 // lane (k = 8 g + jj) or two accumulator tiles of the previous layer (jj = 4 (t & 1) + e  <->  k = 16 t + 4 g + e), so no
-// activation ever changes lane.  Blocks: 0-3 base L0, 4-5 base L1, 6-9 semantics L0, 10-13 colour L0 (K = 16 real + 16
-// zero), 14-21 colour L1.  18 blocks fill the fp32 A region exactly, 4 go to the extension.
+// activation ever changes lane.  Blocks: 0-3 base L0, 4-5 base L1, 6-9 semantics L0, 10-13 colour L0 (K = 16 real: a
+// lane's slots 0-3), 14-21 colour L1.  18 blocks fill the fp32 A region exactly, 4 go to the extension.
 constexpr int BF16_BLOCKS = 22, BF16_BLOCK_FLOATS = 512, BF16_EXT_FLOATS = 4 * BF16_BLOCK_FLOATS;
 
+// Slots 4-7 of blocks 6-13 are zero here (the fp16 images keep them so: their B operand's upper half is zero).  In the
+// split-bf16 images they MIRROR slots 0-3 (bf16_image_word), in the hi and in the lo fragment: the B operand of those
+// blocks carries hi in slots 0-3 and lo in slots 4-7 (render_split.hpp: split_bf16_k16), and two products instead of three
+// give all four hi / lo terms.
 __device__ __forceinline__ float bf16_logical_weight(const PrepArgs& p, int b, int g, int j, int jj) {
   if (b < 4) return p.w0[(16 * b + j) * 32 + 8 * g + jj];
   if (b < 6) return p.w1[j * 64 + 16 * (2 * (b - 4) + (jj >> 2)) + 4 * g + (jj & 3)];
@@ -110,7 +114,8 @@ __device__ __forceinline__ float bf16_image_word(const PrepArgs& p, int q) {  //
   unsigned bits[2];
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
-    const float x = bf16_logical_weight(p, b, lane >> 4, lane & 15, 2 * w + h);
+    const int jj = 2 * w + h;
+    const float x = bf16_logical_weight(p, b, lane >> 4, lane & 15, (b >= 6 && b < 14) ? (jj & 3) : jj);
     const __bf16 hi = (__bf16)x;
     const __bf16 v = half ? (__bf16)(x - (float)hi) : hi;
     bits[h] = (unsigned)__builtin_bit_cast(unsigned short, v);

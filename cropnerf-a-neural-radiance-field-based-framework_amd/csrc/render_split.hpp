@@ -99,6 +99,26 @@ __device__ __forceinline__ f32x4 mfma_split(const bf16x8& ah, const bf16x8& al, 
   return acc;
 }
 
+// A K block that holds only 16 real k values (the 16 base outputs feeding semantics layer 0 and colour layer 0) carries hi AND
+// lo of a lane's four values in one B operand: hi (as split_bf16 defines it) in elements 0-3, lo in elements 4-7 ...
+__device__ __forceinline__ bf16x8 split_bf16_k16(const f32x4& a) {
+  bf16x8 r;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const __bf16 h = (__bf16)a[j];
+    r[j] = h;
+    r[4 + j] = (__bf16)(a[j] - (float)h);
+  }
+  return r;
+}
+// ... and the A images of those blocks repeat a lane's four weights in elements 4-7 (prep_kernel), so two products give all
+// four terms: acc += [ah | ah] . [bh | bl] + [al | al] . [bh | bl] = (ah + al) . (bh + bl)
+__device__ __forceinline__ f32x4 mfma_split_k16(const bf16x8& ah, const bf16x8& al, const bf16x8& b, f32x4 acc) {
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, b, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, b, acc, 0, 0, 0);
+  return acc;
+}
+
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 // eight fp32 values -> the fp16 B operand of v_mfma_f32_16x16x32_f16 (round to nearest even, as __float2half_rn)
@@ -236,7 +256,8 @@ __device__ __forceinline__ void split_fill_edges(const FusedArgs& A, const Split
 }
 
 // MM (cn_render_opts.matrix_precision): MM_BF16 -- the matrix waves run the MLPs on split-bf16 products (the weight images in
-// the blob are then the bf16 ones of prep_kernel, four more blocks of them behind the pair scratch); MM_F16 -- on fp16
+// the blob are then the bf16 ones of prep_kernel, four more blocks of them behind the pair scratch; three products per K
+// block of 32, two for the 16 base outputs, whose one block carries hi and lo: mfma_split_k16); MM_F16 -- on fp16
 // products (v_mfma_f32_16x16x32_f16, fp32 accumulation; tcnn's FullyFusedMLP arithmetic): the gather waves hand over fp16
 // features (16 bytes per lane and sample instead of 32), blended on packed fp16 pairs when the table is a half table.
 // HALF: half2 table entries (CN_TABLE_F16).  GENERIC: per-level index records (tcnn layout), see lane_level_rec.
@@ -790,12 +811,11 @@ __global__ void __launch_bounds__(SPLIT_THREADS) render_split_kernel(FusedArgs A
         }
         // ---- semantics ------------------------------------------------------------------------------------------------------
         float sem_part[2] = {0.f, 0.f};
-        bf16x8 oh[2], ol[2];  // BF16: the 16 base outputs as a K block of 32 (upper half zero)
-        f16x8 o16h[2];        // F16: the same
+        bf16x8 ob[2];   // BF16: the 16 base outputs as a K block of 32, hi in its lower half and lo in its upper half
+        f16x8 o16h[2];  // F16: the 16 base outputs as a K block of 32 (upper half zero)
         if constexpr (BF16) {
-          const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-          for (int c = 0; c < 2; ++c) split_bf16(o16[c], zero4, oh[c], ol[c]);
+          for (int c = 0; c < 2; ++c) ob[c] = split_bf16_k16(o16[c]);
         }
         if constexpr (F16) {
           const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
@@ -814,7 +834,7 @@ __global__ void __launch_bounds__(SPLIT_THREADS) render_split_kernel(FusedArgs A
           } else if constexpr (BF16) {
             const bf16x8 ah = blk(6 + mt)[lane], al = blk(6 + mt)[64 + lane];
 #pragma unroll
-            for (int c = 0; c < 2; ++c) acc[c] = mfma_split(ah, al, oh[c], ol[c], acc[c]);
+            for (int c = 0; c < 2; ++c) acc[c] = mfma_split_k16(ah, al, ob[c], acc[c]);
           } else {
             const f32x4 a = *reinterpret_cast<const f32x4*>(lds + OFF_AS0 + (mt * 64 + lane) * 4);
 #pragma unroll
@@ -839,7 +859,7 @@ __global__ void __launch_bounds__(SPLIT_THREADS) render_split_kernel(FusedArgs A
           } else if constexpr (BF16) {
             const bf16x8 ah = blk(10 + mt)[lane], al = blk(10 + mt)[64 + lane];
 #pragma unroll
-            for (int c = 0; c < 2; ++c) acc[c] = mfma_split(ah, al, oh[c], ol[c], acc[c]);
+            for (int c = 0; c < 2; ++c) acc[c] = mfma_split_k16(ah, al, ob[c], acc[c]);
           } else {
             const f32x4 a = *reinterpret_cast<const f32x4*>(lds + OFF_AC0 + (mt * 64 + lane) * 4);
 #pragma unroll
