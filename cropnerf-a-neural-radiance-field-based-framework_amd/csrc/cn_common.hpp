@@ -468,136 +468,6 @@ __device__ __forceinline__ float2 hash_level_xpair(const void* __restrict__ tabl
   return hash_level_xpair_blend<HALF>(hash_level_xpair_issue<HALF>(table, lv, pos_offset, px, py, pz));
 }
 
-// Private accumulation of the coarsest level's gradient (cn_grid.scatter_scratch): `copies` dense [n1^3][2] arrays,
-// vertex (x, y, z) at x + n1 * (y + n1 * z); a workgroup adds to copy blockIdx.x % copies.  base == nullptr: off.
-struct CoarseScatter {
-  float* base;
-  unsigned n1, copies;
-};
-constexpr unsigned COARSE_COPIES = 64, COARSE_MIN_COPIES = 8, COARSE_MAX_N1 = 40;
-// vertices per axis that level 0 can address for positions in [0, 1]: floor(scale + offset) is the largest cell index
-inline unsigned coarse_n1(const cn_grid& g) {
-  const float off = g.layout == CN_GRID_TCNN ? 0.5f : 0.f;
-  return (unsigned)floorf(g.scalings[0] + off) + 2u;
-}
-inline CoarseScatter make_coarse_scatter(const cn_grid& grads_grid) {
-  CoarseScatter c{nullptr, 0u, 0u};
-  if (!grads_grid.scatter_scratch || grads_grid.num_levels < 1) return c;
-  const unsigned n1 = coarse_n1(grads_grid);
-  if (n1 > COARSE_MAX_N1) return c;
-  const size_t per_copy = (size_t)n1 * n1 * n1 * 2 * sizeof(float);
-  size_t copies = grads_grid.scatter_scratch_bytes / per_copy;
-  if (copies > COARSE_COPIES) copies = COARSE_COPIES;
-  if (copies < COARSE_MIN_COPIES) return c;
-  c.base = static_cast<float*>(grads_grid.scatter_scratch);
-  c.n1 = n1;
-  c.copies = (unsigned)copies;
-  return c;
-}
-
-// Cell-major gradient records of the coarse levels (cn_grid.scatter_scratch, behind the level-0 vertex copies): level l < num_levels
-// keeps copies[l] arrays of n[l]^3 records of 16 floats -- the 8 corners x 2 features of ONE cell, corner c = a + 2 b + 4 d at
-// floats 2c, 2c + 1 -- so that a sample adds its whole cell in ONE 64-byte request (the hash table takes 4.5: one per x-edge),
-// and consecutive samples of a ray in the same cell merge into one.  A fold kernel adds the touched records to the table and
-// zeroes them.  Worth it where samples outnumber cells: the launch picks the levels by batch size.
-constexpr int CN_CELL_LEVELS = 10;
-// A level goes through cell-major records when it has at most (ratio x samples of the call) cells.  Since the fold works by
-// blocks (cell_scatter_fold_blocks_kernel: ~0.4 requests per cell and a streaming pass over the records) a level pays as long as
-// one request per run of samples plus that pass is cheaper than 4.5 requests per sample: measured optimum (tools/train_probe.py,
-// 4 096 / 65 536 rays) at ~2-3 cells per sample for the field (48 samples per ray: few samples share a cell at the
-// fine levels; 3.03 -- 9.5e6 cells, 610 MB of records at 65 536 rays -- already costs 0.6 ms) and 3-8 for the proposal networks
-// (256 / 96 samples per ray: runs merge).  CELL_RATIO_MAX bounds what cn_grid_scatter_scratch_bytes_for sizes the scratch for.
-constexpr double CELL_RATIO_FIELD = 2.85, CELL_RATIO_PROPOSAL = 6.0, CELL_RATIO_MAX = 8.0;
-constexpr unsigned long long CELL_MAX_CELLS = 17500000ull;  // 259^3 fits
-struct CellScatter {
-  float* base;  // nullptr: off
-  int num_levels;
-  unsigned n[CN_CELL_LEVELS];
-  unsigned copies[CN_CELL_LEVELS];
-  unsigned long long offset[CN_CELL_LEVELS];  // in floats from base
-};
-inline unsigned cell_n(const cn_grid& g, int l) {  // cells per axis that positions in [0, 1] can fall into
-  const float off = g.layout == CN_GRID_TCNN ? 0.5f : 0.f;
-  return (unsigned)floorf(g.scalings[l] + off) + 1u;
-}
-inline unsigned cell_copies(unsigned long long ncells) { return ncells <= 8192 ? 16u : ncells <= 65536 ? 4u : 1u; }
-// bytes of the vertex copies (first part of the scratch)
-inline size_t coarse_scratch_bytes(const cn_grid& g) {
-  if (g.num_levels < 1) return 0;
-  const unsigned n1 = coarse_n1(g);
-  return n1 > COARSE_MAX_N1 ? 0 : (size_t)COARSE_COPIES * n1 * n1 * n1 * 2 * sizeof(float);
-}
-// the consecutive coarse levels that may be kept cell-major, and the bytes they need (second part of the scratch)
-inline size_t cell_scratch_layout(const cn_grid& g, CellScatter* out) {
-  CellScatter c{};
-  unsigned long long floats = 0;
-  for (int l = 0; l < g.num_levels && l < CN_CELL_LEVELS; ++l) {
-    const unsigned n = cell_n(g, l);
-    const unsigned long long cells = (unsigned long long)n * n * n;
-    if (cells > CELL_MAX_CELLS) break;
-    c.n[l] = n;
-    c.copies[l] = cell_copies(cells);
-    c.offset[l] = floats;
-    floats += c.copies[l] * cells * 16ull;
-    c.num_levels = l + 1;
-  }
-  if (out) *out = c;
-  return (size_t)floats * sizeof(float);
-}
-// levels 0 .. k-1 with at most max_cells cells each (the launch passes ratio x samples).  Of a small level's copies only as
-// many are used as the batch needs to keep the requests per record in the low hundreds: ~ samples / (48 cells), rounded up
-// to a power of two.
-inline CellScatter make_cell_scatter(const cn_grid& grads_grid, unsigned long long max_cells, unsigned long long samples) {
-  CellScatter c{};
-  if (!grads_grid.scatter_scratch) return c;
-  const size_t head = coarse_scratch_bytes(grads_grid);
-  const size_t need = cell_scratch_layout(grads_grid, &c);
-  if (need == 0 || grads_grid.scatter_scratch_bytes < head) {
-    c = CellScatter{};
-    return c;
-  }
-  // the scratch may hold a PREFIX of the levels (cn_grid_scatter_scratch_bytes_for: sized for a maximum batch): use the
-  // levels whose records fit it
-  int fit = 0;
-  while (fit < c.num_levels) {
-    const unsigned long long cells = (unsigned long long)c.n[fit] * c.n[fit] * c.n[fit];
-    const unsigned long long end = (c.offset[fit] + c.copies[fit] * cells * 16ull) * sizeof(float);
-    if (head + end > grads_grid.scatter_scratch_bytes) break;
-    ++fit;
-  }
-  c.num_levels = fit;
-  int k = 0;
-  while (k < c.num_levels && (unsigned long long)c.n[k] * c.n[k] * c.n[k] <= max_cells) ++k;
-  c.num_levels = k;
-  for (int l = 0; l < k; ++l) {
-    const unsigned long long cells = (unsigned long long)c.n[l] * c.n[l] * c.n[l];
-    unsigned want = 1;
-    while (want < c.copies[l] && (unsigned long long)want * cells * 48ull < samples) want <<= 1;
-    c.copies[l] = want;
-  }
-  c.base = k > 0 ? reinterpret_cast<float*>(static_cast<char*>(grads_grid.scatter_scratch) + head) : nullptr;
-  return c;
-}
-
-__device__ __forceinline__ unsigned cell_n_of(const CellScatter& c, int l) {
-  unsigned v = c.n[0];
-#pragma unroll
-  for (int k = 1; k < CN_CELL_LEVELS; ++k) v = l == k ? c.n[k] : v;
-  return v;
-}
-__device__ __forceinline__ unsigned cell_copies_of(const CellScatter& c, int l) {
-  unsigned v = c.copies[0];
-#pragma unroll
-  for (int k = 1; k < CN_CELL_LEVELS; ++k) v = l == k ? c.copies[k] : v;
-  return v;
-}
-__device__ __forceinline__ unsigned long long cell_offset_of(const CellScatter& c, int l) {
-  unsigned long long v = c.offset[0];
-#pragma unroll
-  for (int k = 1; k < CN_CELL_LEVELS; ++k) v = l == k ? c.offset[k] : v;
-  return v;
-}
-
 // per-lane level record by static selects (a per-lane index into the kernarg arrays would go to scratch)
 __device__ __forceinline__ Lvl lane_level(const GridDev& g, int l) {
   Lvl v = g.level(0);

@@ -20,6 +20,8 @@
 // rounded once, as the first layer's input.  Scratch slices, the reduction and the scatters are the same in both modes.
 #pragma once
 
+#include "train_field_mfma.hpp"  // its mfma_f16x4 / mfma_bf16x4; the unit's shared header
+
 namespace cn {
 namespace gb {
 

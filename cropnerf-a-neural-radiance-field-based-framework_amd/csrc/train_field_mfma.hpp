@@ -1,4 +1,4 @@
-// FruitField backward on the fp32 matrix cores (included by train_field.hip, after FieldBwdArgs and the hash helpers).
+// FruitField backward on the fp32 matrix cores (the default kernel of cn_field_backward; included by train_field.hip).
 //
 // One 512-thread workgroup (8 waves, 2 per SIMD) per CU walks 32-sample tiles.  Per tile the forward is recomputed and
 // every activation / delta lives in LDS as [feature][36] (32 samples + 4 pad: row stride = 4 banks, so the 16-byte and
@@ -20,6 +20,8 @@
 // waves also form W_s0^T d_s1 (the last reader of d_s1 before d_c1 overwrites it) and park it in the d_o16 rows, which the
 // d_o16 phase then adds the colour branch's geo gradient to.  The default instantiations (PSG = false) keep their code.
 #pragma once
+
+#include "train_field_common.hpp"
 
 namespace cn {
 namespace mf {

@@ -1,6 +1,6 @@
-// cn_proposal_backward, round-4 form: ONE WAVE per 64-sample tile (included by train_field.hip after the helpers it uses).
+// cn_proposal_backward, round-4 form: ONE WAVE per 64-sample tile (the default; included by train_field.hip).
 //
-// The first form (proposal_backward_kernel above: four waves share a tile, levels dealt out over the waves, activations in
+// The first form (proposal_backward_kernel, train_proposal_tile.hpp: four waves share a tile, levels dealt out over the waves, activations in
 // LDS, six workgroup barriers per tile) ran at half its atomic-request floor: 2.8 ms per launch at 65 536 rays = 1.2 ms
 // scatter + 0.4 ms weight-gradient dots on the VALU + 1.2 ms of gathers / tiny layers / barriers, one after the other -- per
 // tile a workgroup waits for the slowest wave (the finest level's scatter) five times, wave 0 alone computes positions and the
@@ -19,6 +19,9 @@
 //   * no __syncthreads in the tile loop: sixteen independent waves per CU, each with its own tile, overlap each other's gather
 //     latency, matrix work and atomics.  One barrier at the end folds the four waves' weight gradients before the atomics.
 #pragma once
+
+#include "train_field_common.hpp"
+#include "wave_ops.hpp"
 
 namespace cn {
 namespace pw {

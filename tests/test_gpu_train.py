@@ -739,6 +739,76 @@ def test_deterministic_mode_gives_identical_gradients_and_agrees_with_the_defaul
         assert abs(float(l1[k]) - float(l0[k])) <= 2e-6 * abs(float(l0[k])) + 1e-9, k
 
 
+def test_backward_entry_point_spellings_agree(monkeypatch):
+    """``cn_field_backward`` / ``_mp(CN_MATRIX_FP32)`` / ``_ex(CN_MATRIX_FP32, 0)`` and ``cn_field_backward_general`` / ``_ex(0)`` /
+    ``_mp(0, CN_MATRIX_FP32)`` are three spellings of one call each: under ``CN_DETERMINISTIC_SCATTER=1`` (order-free sums) every
+    gradient tensor, ``d_positions`` and ``d_directions`` are equal bit for bit, each call starting from zeroed gradients.  The
+    gradient grid carries its scatter scratch, so the calls go through the scatter plan and the folds."""
+    import ctypes as C
+
+    from cropnerf_amd import _lib as L
+    from cropnerf_amd import config as PC
+    from cropnerf_amd import ops
+    from oracle import field as OF
+    from oracle import samplers as OSM
+
+    monkeypatch.setenv("CN_DETERMINISTIC_SCATTER", "1")
+    lib = L.load()
+    assert lib.cn_deterministic_build() == 1
+    # the default shape of test_general_field_backward_matches_autograd, its smallest
+    n_img, R = 5, 70
+    shape = dict(geo_feat_dim=15, num_layers_semantic=2, hidden_dim_semantics=64, num_images=n_img)
+    ospec = OF.FieldSpec(grid=OF.GridSpec(16, 16, 2048, 12, 2), **shape)
+    pspec = PC.FieldSpec(grid=PC.GridSpec(16, 16, 2048, 12, 2), **shape)
+    dp = {k: to_dev(v) for k, v in OF.random_params(ospec, [], seed=21, grid_scale=0.1).items() if k.startswith("field.")}
+    fh = ops.FieldHandle(dp, pspec)
+    sc = make_scene(seed=2, log2_T=12, num_images=n_img, height=12, width=12, focal=16.0, prop_log2_T=10)
+    rb = ORY.with_aabb_near_far(ORY.image_rays(sc.c2w, sc.intr, 1, 12, 12), sc.aabb.reshape(-1)).slice(0, R)
+    scene = ops.scene_struct(sc.aabb, True)
+    g = torch.Generator().manual_seed(4)
+    cam = to_dev(torch.randint(0, n_img, (R,), generator=g))
+    ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    ws = torch.empty(lib.cn_field_backward_general_workspace_bytes(C.byref(fh.struct)), dtype=torch.uint8, device="cuda")
+    miss0 = ops.deterministic_misses()
+
+    def spellings(S, calls):
+        rs = OSM.spaced_sampler(rb, S, "uniform")
+        rays = [to_dev(t) for t in (rb.origins, rb.directions)] + [cam] + [to_dev(t[..., 0]) for t in (rs.starts, rs.ends)]
+        up = [to_dev(t) for t in (torch.randn(R, S, generator=g), torch.randn(R, S, 3, generator=g), torch.randn(R, S, generator=g))]
+        results = []
+        for call in calls:
+            # one flat buffer behind every gradient tensor, and the scatter scratch: two registered ranges
+            flat = torch.zeros(sum(v.numel() for v in dp.values()), device="cuda")
+            grads, off = {}, 0
+            for k, v in dp.items():
+                grads[k] = flat[off:off + v.numel()].view_as(v)
+                off += v.numel()
+            gh = ops.FieldHandle(grads, pspec).enable_scatter_scratch(R * S)
+            assert gh._scatter_scratch is not None
+            ops.deterministic_register([flat, gh._scatter_scratch], owner=flat)
+            d_pos, d_dir = torch.zeros(R, S, 3, device="cuda"), torch.zeros(R, S, 3, device="cuda")
+            head = (C.byref(fh.struct), C.byref(gh.struct), C.byref(scene), L.APP_PER_CAMERA, 1, None,
+                    *(ptr(t) for t in rays), *(ptr(u) for u in up), R, S, ptr(d_pos), ptr(d_dir))
+            L.check(call(head))
+            torch.cuda.synchronize()
+            assert float(gh._scatter_scratch.abs().max()) == 0.0  # left zeroed
+            results.append({**{k: v.clone() for k, v in grads.items()}, "d_positions": d_pos, "d_directions": d_dir})
+        ref = results[0]
+        assert all(float(v.abs().sum()) > 0 for v in ref.values())
+        for i, got in enumerate(results[1:], 1):
+            for k in ref:
+                assert torch.equal(got[k], ref[k]), (S, i, k)
+
+    # 70 x 48 = 3 360 samples: 52 whole 64-sample tiles and a ragged one
+    spellings(48, [lambda h: lib.cn_field_backward(*h, None),
+                   lambda h: lib.cn_field_backward_mp(*h, L.MATRIX_FP32, None),
+                   lambda h: lib.cn_field_backward_ex(*h, L.MATRIX_FP32, 0, None)])
+    spellings(16, [lambda h: lib.cn_field_backward_general(*h, ptr(ws), ws.numel(), None),
+                   lambda h: lib.cn_field_backward_general_ex(*h, 0, ptr(ws), ws.numel(), None),
+                   lambda h: lib.cn_field_backward_general_mp(*h, 0, L.MATRIX_FP32, ptr(ws), ws.numel(), None)])
+    assert ops.deterministic_misses() == miss0, "a backward kernel added to a buffer that is not registered"
+
+
 def test_graph_replay_equals_eager_bit_for_bit_in_deterministic_mode(monkeypatch):
     """The comparison ``test_graph_replayed_iteration_follows_the_eager_one`` can only bound loosely (float-atomic orders, Adam's
     normalisation), made exact: under ``CN_DETERMINISTIC_SCATTER=1`` sixteen graph-replayed iterations and sixteen eager ones --
