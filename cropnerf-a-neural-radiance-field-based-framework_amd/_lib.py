@@ -195,6 +195,8 @@ SIGNATURES = {
     "cn_zbuffer_workspace_bytes": (C.c_size_t, [_I32, _I32]),
     "cn_zbuffer_update_large": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, C.c_size_t, _P]),
     "cn_zbuffer_update": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, C.c_size_t, _P]),
+    "cn_splat_workspace_bytes": (C.c_size_t, [_I32, _I32, _I32]),
+    "cn_splat_points": (C.c_int, [_P, _P, _I64, _P, _I32, _I32, _I32, _I32, _F, C.c_uint32, _P, _P, _P, _P, C.c_size_t, _P]),
     "cn_knn_mean_distance": (C.c_int, [_P, _P, _I32, _I32, _I32, _F, _F, _F, _F, _I64, _I32, _P, _P]),
     "cn_estimate_normals": (C.c_int, [_P, _P, _I32, _I32, _I32, _F, _F, _F, _F, _I64, _I32, _P, _P, _P]),
     "cn_knn_mean_distance_grid": (C.c_int, [_P, C.POINTER(PointGrid), _I64, _I32, _P, _P]),

@@ -1209,6 +1209,55 @@ def zbuffer_update(z_buffer: Tensor, img: Tensor, xs: Tensor, ys: Tensor, zs: Te
 
 
 # --------------------------------------------------------------------------------------------------------------
+# views of a (labelled) point cloud: z-tested point splat into many pinhole frames (csrc/splat.hip)
+# --------------------------------------------------------------------------------------------------------------
+
+SPLAT_WORKSPACE_BUDGET = 256 << 20  # bytes of key buffer per launch: frames are chunked to stay under it
+
+
+def splat_points(points: Tensor, colors: Tensor, cameras: Tensor, height: int, width: int, point_size: int = 2,
+                 near_plane: float = 1e-3, background: Sequence[int] = (255, 255, 255), return_index: bool = False,
+                 return_depth: bool = False, max_frames_per_launch: Optional[int] = None):
+    """``cn_splat_points``: ``points`` [N,3] float32 with ``colors`` [N,3] uint8 drawn into the F frames of ``cameras``
+    [F,16] float32 (world-to-camera 3x4 row-major, then fx, fy, cx, cy; the geometry is defined in
+    ``include/cropnerf_hip.h``).  Returns ``images`` [F,H,W,3] uint8, or a tuple with ``index`` [F,H,W] int32 (-1 = empty)
+    and / or ``depth`` [F,H,W] float32 (+inf = empty) appended when asked for.  The frames go through the kernel
+    ``max_frames_per_launch`` at a time (default: what fits ``SPLAT_WORKSPACE_BUDGET`` of key buffer, at least one)."""
+    lib = L.load()
+    stream = _stream(points)
+    pts = _f32(points, "points")
+    cams = _f32(cameras, "cameras")
+    _dev(colors, torch.uint8, "colors")
+    if pts.dim() != 2 or pts.shape[1] != 3 or tuple(colors.shape) != tuple(pts.shape):
+        raise ValueError(f"splat_points: points {tuple(pts.shape)} / colors {tuple(colors.shape)}, expected [N,3] both")
+    if cams.dim() != 2 or cams.shape[1] != 16:
+        raise ValueError(f"splat_points: cameras {tuple(cams.shape)}, expected [F,16]")
+    F, H, W, n = cams.shape[0], int(height), int(width), pts.shape[0]
+    per_launch = max(1, SPLAT_WORKSPACE_BUDGET // max(1, H * W * 8)) if max_frames_per_launch is None else int(max_frames_per_launch)
+    if per_launch < 1:
+        raise ValueError("splat_points: max_frames_per_launch must be at least 1")
+    per_launch = min(per_launch, max(F, 1))
+    r, g, b = (int(v) for v in background)
+    if not all(0 <= v <= 255 for v in (r, g, b)):
+        raise ValueError("splat_points: background is three bytes (r, g, b)")
+    dev = pts.device
+    images = torch.empty(F, H, W, 3, dtype=torch.uint8, device=dev)
+    index = torch.empty(F, H, W, dtype=torch.int32, device=dev) if return_index else None
+    depth = torch.empty(F, H, W, dtype=torch.float32, device=dev) if return_depth else None
+    ws_bytes = lib.cn_splat_workspace_bytes(per_launch, H, W)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    for f0 in range(0, F, per_launch):
+        nf = min(per_launch, F - f0)
+        L.check(lib.cn_splat_points(_p(pts), _p(colors), n, _p(cams[f0:f0 + nf]), nf, H, W, int(point_size), float(near_plane),
+                                    r | (g << 8) | (b << 16), _p(images[f0:f0 + nf]),
+                                    _p(None if index is None else index[f0:f0 + nf]),
+                                    _p(None if depth is None else depth[f0:f0 + nf]), C.c_void_p(ws.data_ptr()), ws_bytes,
+                                    stream))
+    out = (images,) + ((index,) if return_index else ()) + ((depth,) if return_depth else ())
+    return images if len(out) == 1 else out
+
+
+# --------------------------------------------------------------------------------------------------------------
 # statistical outlier removal (open3d remove_statistical_outlier as used by the point-cloud exporter)
 # --------------------------------------------------------------------------------------------------------------
 

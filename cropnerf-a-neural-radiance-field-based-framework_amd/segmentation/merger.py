@@ -206,7 +206,8 @@ def count_from_projection_dir(projection_dir, n_super_clusters: int, n_sub_clust
 
 def main(argv=None) -> int:
     """``python -m cropnerf_amd.segmentation.merger --base_dir D --recording_name R`` -- the reference's arguments
-    (``:359-378``); reads ``D/artifacts/R/projection`` and ``D/artifacts/R/pcd/all_super_cluster_info.npy``."""
+    (``:359-378``); reads ``D/artifacts/R/projection`` and ``D/artifacts/R/pcd/all_super_cluster_info.npy``.  With
+    ``--visualize`` (off unless given) it also writes the labelled cloud and its orbit frames (``write_result_views``)."""
     import argparse
     import os
 
@@ -220,19 +221,52 @@ def main(argv=None) -> int:
     ap.add_argument("--super_cluster_idx", type=int, default=-1)
     ap.add_argument("--binary_threshold", type=int, default=100)
     ap.add_argument("--frame_sampling_interval", type=int, default=10)
+    # the reference's viewer flags (:368-369).  --visualize is OFF by default here: the run then prints the count and writes nothing
+    truth = lambda v: str(v).lower() in ("1", "true", "yes")
+    ap.add_argument("--visualize", type=truth, nargs="?", const=True, default=False)
+    ap.add_argument("--vis_full_tree", type=truth, nargs="?", const=True, default=True)
+    ap.add_argument("--vis_num_frames", type=int, default=180)
+    ap.add_argument("--vis_width", type=int, default=1920)
+    ap.add_argument("--vis_height", type=int, default=1080)
     a = ap.parse_args(argv)
     projection_dir = os.path.join(a.base_dir, "artifacts", a.recording_name, "projection")
     pcd = np.load(os.path.join(a.base_dir, "artifacts", a.recording_name, "pcd", "all_super_cluster_info.npy"), allow_pickle=True)
     n_sc, k = (min(17, len(pcd)) if a.super_cluster_idx == -1 else 1), pcd[0]["aabb"].shape[0]  # :398-399,421
     if a.super_cluster_idx != -1:
         raise SystemExit("a single --super_cluster_idx: rename that directory to super_cluster_0 or use the Python API")
-    total, counts, _, _ = count_from_projection_dir(projection_dir, n_sc, k, a.graph_partition, a.binary_threshold,
-                                                    a.frame_sampling_interval, a.area_normalize, a.visible_img_prefix,
-                                                    a.wo_occ_img_prefix)
+    total, counts, labels_all, _ = count_from_projection_dir(projection_dir, n_sc, k, a.graph_partition, a.binary_threshold,
+                                                             a.frame_sampling_interval, a.area_normalize, a.visible_img_prefix,
+                                                             a.wo_occ_img_prefix)
     for i, n in enumerate(counts):
         print(f"{i}_th super cluster has: {n}.")
     print(f"Total bool: {total}")  # sic (:437)
+    if a.visualize:
+        write_result_views(os.path.join(a.base_dir, "artifacts", a.recording_name, "pcd"), pcd, labels_all, a.vis_full_tree,
+                           a.vis_num_frames, a.vis_width, a.vis_height)
     return total
+
+
+def write_result_views(pcd_dir, pcd_data, labels_all, vis_full_tree: bool = True, num_frames: int = 180, width: int = 1920,
+                       height: int = 1080):
+    """What ``--visualize`` leaves of the reference's viewer (``:446-460``): ``pcd_dir/full_tree_seg_result.ply`` -- every
+    sub-cluster painted with its instance label, colours as ``show_pcd`` (``:105-110``) -- and the orbit of
+    ``evaluation/generate_video.py`` over that cloud as ``pcd_dir/full_tree_seg_result_frames/frame_%05d.png``, with
+    ``pcd_dir/full_tree_pc.ply`` as grey context when ``vis_full_tree`` is set and the file exists."""
+    import os
+
+    from ..fruit_nerf.ply import read_ply, write_ply
+    from . import result_cloud, video_renderer
+
+    points, labels = result_cloud.labelled_result(pcd_data, labels_all)
+    colors = result_cloud.label_colors(labels, normalise=True)
+    ply_path = os.path.join(str(pcd_dir), "full_tree_seg_result.ply")
+    write_ply(ply_path, points, (colors.astype(np.float64) + 0.5) / 255.0)  # write_ply truncates colour * 255: the bytes as they are
+    tree_path = os.path.join(str(pcd_dir), "full_tree_pc.ply")
+    full_tree = read_ply(tree_path)[0] if vis_full_tree and os.path.exists(tree_path) else None
+    frames = video_renderer.pointcloud_to_frames(points, colors, None, full_tree,
+                                                 os.path.join(str(pcd_dir), "full_tree_seg_result_frames"), width=width,
+                                                 height=height, num_frames=num_frames)
+    return ply_path, frames
 
 
 if __name__ == "__main__":

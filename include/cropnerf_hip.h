@@ -752,6 +752,34 @@ int cn_zbuffer_update(const int32_t* xs, const int32_t* ys, const double* zs, in
                       size_t workspace_bytes, cn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Views of a (labelled) point cloud without a window: a z-tested point splat of one cloud into num_frames pinhole
+ * frames at once -- what the reference's viewers get from an open3d window with render_opt.point_size
+ * (evaluation/generate_video.py:17-117, segmentation/video_renderer.py, evaluation/vis_semantic_seg.py).
+ *
+ * Geometry (cameras [F,16] per frame: the world-to-camera 3x4 [R | t] row-major, then fx, fy, cx, cy):
+ *   - Camera space is c = R p + t, with x right, y down and z forward.  This is open3d's extrinsic convention.
+ *   - A point with c.z <= near_plane is dropped.
+ *   - u = fx * c.x / c.z + cx and v = fy * c.y / c.z + cy.  Pixel centres sit at integer coordinates.
+ *   - The point covers the columns j with u - s/2 <= j < u + s/2, that is j = ceil(u - s/2) ... ceil(u + s/2) - 1.
+ *   - It covers the rows i the same way from v.  Here s = point_size >= 1.
+ *   - The footprint is clipped to the image.  A footprint entirely outside the image contributes nothing.
+ * Per pixel the winner is the smallest c.z in float32; ties go to the smallest point index, so the result is a pure
+ * function of the inputs, whatever order the waves run in.  (The kernel computes in float32 with fused multiply-adds:
+ * a footprint edge within rounding of a pixel boundary can fall either way against a float64 evaluation.)
+ *
+ * images [F,H,W,3] uint8: the winner's colour (colors [N,3] uint8) or background_rgb (0x00BBGGRR: red in the low byte).
+ * index [F,H,W] (optional): the winning point, -1 = empty; points 2^31 and above appear as their uint32 bit pattern.
+ * depth [F,H,W] (optional): camera z of the winner, +inf = empty.  workspace: 8 bytes per pixel per frame.
+ * num_points == 0 is valid (background frames); num_points must be below 2^32 and near_plane >= 0.  Every argument error
+ * is CN_ERR_INVALID.
+ * ------------------------------------------------------------------------------------------- */
+size_t cn_splat_workspace_bytes(int32_t num_frames, int32_t height, int32_t width);
+int cn_splat_points(const float* points, const uint8_t* colors, int64_t num_points, const float* cameras,
+                    int32_t num_frames, int32_t height, int32_t width, int32_t point_size, float near_plane,
+                    uint32_t background_rgb, uint8_t* images, int32_t* index, float* depth, void* workspace,
+                    size_t workspace_bytes, cn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Statistical outlier removal of the point-cloud exporter: the k-nearest-neighbour pass of open3d's
  * remove_statistical_outlier(nb_neighbors=20, std_ratio) as called at
  * fruit_nerf/export/exporter_utils_nerfacto.py:194-199.  The caller bins the points on a uniform grid
