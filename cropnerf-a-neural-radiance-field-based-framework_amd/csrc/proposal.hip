@@ -82,6 +82,12 @@ struct PropArgs {
 // multiply-adds per lane and tile plus a three-step butterfly over the four lane groups that leaves evaluation l in lane l.
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int PROP_ENC_STRIDE = 80;  // per wave: [enc_rows][80] floats, enc_rows = 12 (5-level nets) or 16 (7 levels)
+// dynamic LDS of a workgroup (four waves): the sampler arrays [4 smax + 4] and the encoding block [enc_rows][80] of each wave
+constexpr size_t prop_sample_lds_bytes(int smax, int enc_rows) {
+  return ((size_t)4 * (4 * (size_t)smax + 4) + (size_t)4 * enc_rows * PROP_ENC_STRIDE) * sizeof(float);
+}
+static_assert(prop_sample_lds_bytes(PROP_MAX_SAMPLES, 16) == 53312 && prop_sample_lds_bytes(PROP_MAX_SAMPLES, 16) <= 65536,
+              "the largest accepted shape (512 samples, a 7-level net) fits the 64 KiB every launch is granted");
 struct PropMlp {
   float a[4];   // W0[m = lane & 15][k = 4 kb + (lane >> 4)], kb < K / 4 (0 for k >= 2L)
   f32x4 b0;     // b0[4 q + r]
@@ -431,7 +437,7 @@ static int proposal_sample_launch(const char* who, const cn_density_params* cons
   A.final_ends = final_ends;
   A.enc_rows = 0;
   for (int l = 0; l < num_levels; ++l) A.enc_rows = std::max(A.enc_rows, (2 * A.net[l].grid.num_levels + 3) / 4 * 4);
-  const size_t lds = ((size_t)4 * (4 * A.smax + 4) + (size_t)4 * A.enc_rows * PROP_ENC_STRIDE) * sizeof(float);
+  const size_t lds = prop_sample_lds_bytes(A.smax, A.enc_rows);
   const dim3 grid(grid_for(num_rays, 4, 256 * 8)), block(256);
   const bool half = A.net[0].grid.half;
 #define CN_PROP_LAUNCH(H, T) hipLaunchKernelGGL((proposal_sample_kernel<H, T>), grid, block, lds, as_stream(stream), A)

@@ -67,6 +67,12 @@ sample_pdf_kernel(const float* __restrict__ prev_bins, const float* __restrict__
   }
 }
 
+// dynamic LDS of sample_pdf_kernel (four waves), and the longest input row whose workgroup fits 64 KiB
+constexpr size_t sample_pdf_lds_bytes(int s_in) { return (size_t)4 * (3 * (size_t)s_in + 2) * sizeof(float); }
+constexpr int SAMPLE_PDF_MAX_IN = 1364;
+static_assert(sample_pdf_lds_bytes(SAMPLE_PDF_MAX_IN) <= 65536 && sample_pdf_lds_bytes(SAMPLE_PDF_MAX_IN + 1) > 65536,
+              "SAMPLE_PDF_MAX_IN is the largest s_in within 64 KiB");
+
 }  // namespace cn
 
 extern "C" int cn_sample_spaced(const float* nears, const float* fars, int64_t num_rays, int32_t num_samples,
@@ -90,12 +96,16 @@ extern "C" int cn_sample_pdf(const float* prev_spacing_bins, const float* weight
                              int32_t spacing, const float* u_rand, int32_t u_rand_stride, float* spacing_bins,
                              float* euclidean_bins, cn_stream_t stream) {
   CN_REQUIRE(prev_spacing_bins && weights && nears && fars, CN_ERR_INVALID, "cn_sample_pdf: null input");
-  CN_REQUIRE(s_in > 0 && s_in <= 4096 && s_out > 0, CN_ERR_INVALID, "cn_sample_pdf: bad sample counts %d -> %d", s_in,
-             s_out);
+  CN_REQUIRE(s_in > 0 && s_out > 0, CN_ERR_INVALID, "cn_sample_pdf: bad sample counts %d -> %d", s_in, s_out);
+  // Four waves per workgroup, 3 s_in + 2 floats each: 16 (3 s_in + 2) bytes of dynamic LDS.  Held to the 64 KiB every launch is
+  // granted without opting in to more: 3 s_in + 2 <= 4096, s_in <= 1364 (65 504 B).  Refused here, never at the launch.
+  CN_REQUIRE(s_in <= cn::SAMPLE_PDF_MAX_IN, CN_ERR_UNSUPPORTED,
+             "cn_sample_pdf: s_in %d (max %d: %zu bytes of LDS per workgroup, limit 65536)", s_in, cn::SAMPLE_PDF_MAX_IN,
+             cn::sample_pdf_lds_bytes(s_in));
   CN_REQUIRE(!u_rand || u_rand_stride == 1 || u_rand_stride == s_out + 1, CN_ERR_INVALID,
              "cn_sample_pdf: u_rand_stride must be 1 or S_out+1");
   if (num_rays <= 0) return CN_OK;
-  size_t lds = (size_t)4 * (3 * s_in + 2) * sizeof(float);
+  const size_t lds = cn::sample_pdf_lds_bytes(s_in);
   hipLaunchKernelGGL(cn::sample_pdf_kernel, dim3(cn::grid_for(num_rays, 4, 4096)), dim3(256), lds,
                      cn::as_stream(stream), prev_spacing_bins, weights, nears, fars, (long long)num_rays, s_in, s_out,
                      anneal, spacing, u_rand, u_rand_stride, spacing_bins, euclidean_bins);

@@ -499,6 +499,9 @@ def sample_spaced(nears: Tensor, fars: Tensor, num_samples: int, spacing: int = 
 def sample_pdf(prev_spacing_bins: Tensor, weights: Tensor, nears: Tensor, fars: Tensor, num_samples: int,
                anneal: float = 1.0, spacing: int = L.SPACING_PIECEWISE, u_rand: Optional[Tensor] = None
                ) -> Tuple[Tensor, Tensor]:
+    """``cn_sample_pdf``: one PDF resampling step, ``weights`` [R, s_in] on ``prev_spacing_bins`` [R, s_in + 1] -> spacing and
+    euclidean bins [R, num_samples + 1].  ``s_in`` is at most 1364: a workgroup (four rays) keeps 16 (3 s_in + 2) bytes in LDS,
+    held to 64 KiB; longer rows raise ``CropNerfHipError`` (``CN_ERR_UNSUPPORTED``) before anything is launched."""
     lib = L.load()
     R, s_in = weights.shape
     dev = weights.device

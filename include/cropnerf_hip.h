@@ -358,7 +358,9 @@ int cn_sample_spaced(const float* nears, const float* fars, int64_t num_rays, in
 /* PDFSampler.generate_ray_samples (nerfstudio; called through ProposalNetworkSampler at
  * fruit_nerf/fruit_nerf.py:157-164,549).  Inputs: previous spacing bins [R,S_in+1] and weights [R,S_in]
  * (already annealed by the caller or via `anneal`: w^anneal).  u_rand NULL = eval.
- * Outputs: spacing bins [R,S_out+1] and euclidean bins [R,S_out+1]. */
+ * Outputs: spacing bins [R,S_out+1] and euclidean bins [R,S_out+1].
+ * S_in <= 1364: a workgroup (four rays) keeps 16 (3 S_in + 2) bytes in LDS, held to 64 KiB; a longer row is
+ * CN_ERR_UNSUPPORTED, refused on the host before any launch. */
 int cn_sample_pdf(const float* prev_spacing_bins, const float* weights, const float* nears, const float* fars,
                   int64_t num_rays, int32_t s_in, int32_t s_out, float anneal, int32_t spacing,
                   const float* u_rand, int32_t u_rand_stride, float* spacing_bins, float* euclidean_bins,

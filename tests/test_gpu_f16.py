@@ -167,6 +167,47 @@ def test_unknown_matrix_precision_is_rejected(ops, L):
         ops.render_rays(fh, ops.scene_struct(scene.aabb, False), ops.render_opts(64, matrix_precision=7), *args)
 
 
+def _fp16_sampler_case(ops, L, second_prop, s_prop=(256, 96), s_final=48, first_prop=(5, 128), num_rays=600):
+    scene = make_tcnn_scene(seed=3, grid_scale=1.0, second_prop=second_prop, first_prop=first_prop)
+    fspec, pspecs = product_specs(scene)
+    dp16 = dev_params(scene, table_dtype=torch.float16)
+    fh = ops.FieldHandle(dp16, fspec)
+    dh = [ops.DensityHandle(dp16, i, ps) for i, ps in enumerate(pspecs)]
+    assert all(dp16[f"proposal_networks.{i}.encoding.hash_table"].dtype == torch.float16 for i in range(len(pspecs)))
+    assert pspecs[1].grid.num_levels == second_prop[0]
+    rb = ORY.image_rays(scene.c2w, scene.intr, 5, scene.height, scene.width).slice(0, num_rays)
+    half = dataclasses.replace(scene, fspec=dataclasses.replace(scene.fspec, tcnn_half_activations=True),
+                               pspecs=[dataclasses.replace(p, tcnn_half_activations=True) for p in scene.pspecs])
+    ref = oracle_model(half, "test", num_proposal_samples_per_ray=tuple(s_prop), num_nerf_samples_per_ray=s_final).forward(rb)
+    o, d = to_dev(rb.origins).clone(), to_dev(rb.directions).clone()
+    ops.apply_pose_adjustment(dp16["camera_optimizer.pose_adjustment"], to_dev(rb.camera_indices[:, 0]), o, d)
+    R = len(rb)
+    nears, fars = torch.zeros(R, 1, device="cuda"), torch.full((R, 1), 1000.0, device="cuda")
+    sc = ops.scene_struct(scene.aabb, True)
+    ps16 = ops.proposal_sample(dh, sc, o, d, nears, fars, s_prop, s_final, matrix_precision=L.MATRIX_F16)
+    ps32 = ops.proposal_sample(dh, sc, o, d, nears, fars, s_prop, s_final)
+    ref_bins = torch.cat([ref["_starts"][..., 0], ref["_ends"][:, -1:, 0]], -1)
+    got = ps16["euclidean_bins"].cpu()
+    width = (ref_bins[:, 1:] - ref_bins[:, :-1]).clamp_min(1e-9)
+    width = torch.cat([width, width[:, -1:]], -1)
+    dev_frac = (got - ref_bins).abs() / width
+    assert float((dev_frac <= 0.02).float().mean()) >= 0.999, f"bin edges: worst {float(dev_frac.max()):.3g} of a bin width"
+    assert not torch.equal(ps16["euclidean_bins"], ps32["euclidean_bins"])  # it IS another arithmetic
+    assert float((ps16["euclidean_bins"] - ps32["euclidean_bins"]).abs().max()) < 1e-2
+    out = ops.render_rays(fh, sc, ops.render_opts(s_final, matrix_precision=L.MATRIX_F16), o, d, nears, fars,
+                          bins=ps16["euclidean_bins"], camera_indices=None)
+    assert_close(out["rgb"], ref["rgb"], 0.0, 5e-4, "rgb: fp16 sampler + fp16 render vs the half-activation oracle")
+    assert_close(out["accumulation"], ref["accumulation"], 2e-4, 5e-5, "accumulation")
+    # float tables: the mode has no fp16 sampler to offer and must not change a bit
+    dp32 = dev_params(scene, table_dtype=torch.float32)
+    dh32 = [ops.DensityHandle(dp32, i, ps) for i, ps in enumerate(pspecs)]
+    a = ops.proposal_sample(dh32, sc, o, d, nears, fars, s_prop, s_final, matrix_precision=L.MATRIX_F16)
+    b = ops.proposal_sample(dh32, sc, o, d, nears, fars, s_prop, s_final)
+    assert torch.equal(a["euclidean_bins"], b["euclidean_bins"])
+    with pytest.raises(L.CropNerfHipError, match="matrix_precision"):
+        ops.proposal_sample(dh, sc, o, d, nears, fars, s_prop, s_final, matrix_precision=9)
+
+
 @pytest.mark.parametrize("second_prop", [(5, 256), (7, 2048)])  # the default method's second network / fruit_nerf_method_big's
 def test_proposal_sampler_in_fp16_mode(ops, L, second_prop):
     """``cn_proposal_sample_mp`` with ``CN_MATRIX_F16`` on half tables: the proposal networks in tiny-cuda-nn's arithmetic class
@@ -176,44 +217,19 @@ def test_proposal_sampler_in_fp16_mode(ops, L, second_prop):
     resampled bins to a small fraction of a bin: stated bar 2 % of the bin's own width for 99.9 % of the edges [measured
     worst case in the message], and everything downstream -- a render on those bins -- inside the fp16 render bars.  A float
     table keeps the fp32 sampler (same bits as ``cn_proposal_sample``)."""
-    scene = make_tcnn_scene(seed=3, grid_scale=1.0, second_prop=second_prop)
-    fspec, pspecs = product_specs(scene)
-    dp16 = dev_params(scene, table_dtype=torch.float16)
-    fh = ops.FieldHandle(dp16, fspec)
-    dh = [ops.DensityHandle(dp16, i, ps) for i, ps in enumerate(pspecs)]
-    assert all(dp16[f"proposal_networks.{i}.encoding.hash_table"].dtype == torch.float16 for i in range(len(pspecs)))
-    assert pspecs[1].grid.num_levels == second_prop[0]
-    rb = ORY.image_rays(scene.c2w, scene.intr, 5, scene.height, scene.width).slice(0, 600)
-    half = dataclasses.replace(scene, fspec=dataclasses.replace(scene.fspec, tcnn_half_activations=True),
-                               pspecs=[dataclasses.replace(p, tcnn_half_activations=True) for p in scene.pspecs])
-    ref = oracle_model(half, "test").forward(rb)
-    o, d = to_dev(rb.origins).clone(), to_dev(rb.directions).clone()
-    ops.apply_pose_adjustment(dp16["camera_optimizer.pose_adjustment"], to_dev(rb.camera_indices[:, 0]), o, d)
-    R = len(rb)
-    nears, fars = torch.zeros(R, 1, device="cuda"), torch.full((R, 1), 1000.0, device="cuda")
-    sc = ops.scene_struct(scene.aabb, True)
-    ps16 = ops.proposal_sample(dh, sc, o, d, nears, fars, (256, 96), 48, matrix_precision=L.MATRIX_F16)
-    ps32 = ops.proposal_sample(dh, sc, o, d, nears, fars, (256, 96), 48)
-    ref_bins = torch.cat([ref["_starts"][..., 0], ref["_ends"][:, -1:, 0]], -1)
-    got = ps16["euclidean_bins"].cpu()
-    width = (ref_bins[:, 1:] - ref_bins[:, :-1]).clamp_min(1e-9)
-    width = torch.cat([width, width[:, -1:]], -1)
-    dev_frac = (got - ref_bins).abs() / width
-    assert float((dev_frac <= 0.02).float().mean()) >= 0.999, f"bin edges: worst {float(dev_frac.max()):.3g} of a bin width"
-    assert not torch.equal(ps16["euclidean_bins"], ps32["euclidean_bins"])  # it IS another arithmetic
-    assert float((ps16["euclidean_bins"] - ps32["euclidean_bins"]).abs().max()) < 1e-2
-    out = ops.render_rays(fh, sc, ops.render_opts(48, matrix_precision=L.MATRIX_F16), o, d, nears, fars,
-                          bins=ps16["euclidean_bins"], camera_indices=None)
-    assert_close(out["rgb"], ref["rgb"], 0.0, 5e-4, "rgb: fp16 sampler + fp16 render vs the half-activation oracle")
-    assert_close(out["accumulation"], ref["accumulation"], 2e-4, 5e-5, "accumulation")
-    # float tables: the mode has no fp16 sampler to offer and must not change a bit
-    dp32 = dev_params(scene, table_dtype=torch.float32)
-    dh32 = [ops.DensityHandle(dp32, i, ps) for i, ps in enumerate(pspecs)]
-    a = ops.proposal_sample(dh32, sc, o, d, nears, fars, (256, 96), 48, matrix_precision=L.MATRIX_F16)
-    b = ops.proposal_sample(dh32, sc, o, d, nears, fars, (256, 96), 48)
-    assert torch.equal(a["euclidean_bins"], b["euclidean_bins"])
-    with pytest.raises(L.CropNerfHipError, match="matrix_precision"):
-        ops.proposal_sample(dh, sc, o, d, nears, fars, (256, 96), 48, matrix_precision=9)
+    _fp16_sampler_case(ops, L, second_prop)
+
+
+@pytest.mark.parametrize("method", ["fruit_nerf_big", "fruit_nerf_huge"])
+def test_proposal_sampler_in_fp16_mode_at_the_shipped_counts(ops, L, method):
+    """The same, under the same bars, at the counts and proposal networks of the two large shipped methods ((512, 256) -> 128 and
+    (512, 512) -> 64, read from ``fruit_nerf_config.py``): eight 64-lane chunks per ray in the fp16 form of the sampler."""
+    from cropnerf_amd.fruit_nerf.fruit_nerf_config import native_method
+
+    cfg = native_method(method).config.pipeline.model
+    nets = [cfg.proposal_net_args_list[min(i, len(cfg.proposal_net_args_list) - 1)] for i in range(cfg.num_proposal_iterations)]
+    first, second = [(a["num_levels"], a["max_res"]) for a in nets]
+    _fp16_sampler_case(ops, L, second, tuple(cfg.num_proposal_samples_per_ray), cfg.num_nerf_samples_per_ray, first, num_rays=300)
 
 
 @pytest.mark.parametrize("mode", ["f16", "split_bf16"])
