@@ -25,7 +25,7 @@ OUT_DET = HERE / "libcropnerf_hip_det.so"  # the deterministic-accumulation test
 DET_SOURCES = ["train_render.hip", "train_field.hip", "tcnn_grid.hip", "deterministic.hip"]  # compiled again with the macro
 
 SOURCES = ["api_common.cpp", "deterministic.hip", "raygen.hip", "sampler.hip", "field_simple.hip", "composite.hip", "render_fused.hip",
-           "proposal.hip", "export.hip", "train_render.hip", "train_field.hip", "zbuffer.hip", "splat.hip", "knn.hip", "cluster.hip", "tcnn_grid.hip", "contour.hip", "projection.hip", "uncertainty.hip",
+           "proposal.hip", "export.hip", "train_render.hip", "train_field.hip", "zbuffer.hip", "splat.hip", "knn.hip", "cluster.hip", "tcnn_grid.hip", "contour.hip", "labels.hip", "projection.hip", "uncertainty.hip",
            "png_writer.cpp"]
 
 

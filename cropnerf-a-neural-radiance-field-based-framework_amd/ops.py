@@ -1505,6 +1505,32 @@ def contour_largest(gray: Tensor, thresh: int, roi: Optional[Tensor] = None, lab
     return out
 
 
+def instance_labels(frames: Tensor) -> Dict[str, Tensor]:
+    """``cn_instance_labels`` on a batch of colour instance masks [F,H,W,3] uint8 RGB (device): ``labels`` [F,H,W] uint8 --
+    0 for black, else 1 + the number of smaller distinct keys ``B << 16 | G << 8 | R`` of the same frame --, ``colors``
+    [F,256] int32 (the key of each label, 0 for label 0 and past the frame's count) and ``num_colors`` [F] int32.  Reads
+    ``num_colors`` back once (the call's one synchronisation) and raises ``ValueError`` naming the frames that hold more
+    than 255 colours."""
+    frames = _u8(frames, "frames")
+    if frames is None or frames.dim() != 4 or frames.shape[3] != 3:
+        raise ValueError(f"frames: expected [F,H,W,3] RGB, got {None if frames is None else tuple(frames.shape)}")
+    lib = L.load()
+    F, H, W, _ = frames.shape
+    dev = frames.device
+    out = {"labels": torch.empty(F, H, W, dtype=torch.uint8, device=dev),
+           "colors": torch.zeros(F, 256, dtype=torch.int32, device=dev),
+           "num_colors": torch.zeros(F, dtype=torch.int32, device=dev)}
+    if F == 0 or H * W == 0:
+        return out
+    ws = torch.empty(int(lib.cn_instance_labels_workspace_bytes(F)), dtype=torch.uint8, device=dev)
+    L.check(lib.cn_instance_labels(_p(frames), F, H, W, _p(out["labels"]), _p(out["colors"]), _p(out["num_colors"]), _p(ws),
+                                   ws.numel(), _stream(frames)))
+    over = (out["num_colors"].cpu() > 255).nonzero().flatten().tolist()
+    if over:
+        raise ValueError(f"instance_labels: more than 255 non-black colours in frame(s) {over} of the batch")
+    return out
+
+
 def kmeans(points: Tensor, k: int, max_iter: int = 300, tol: float = 1e-4, random_state: int = 0) -> Tensor:
     """``sklearn.cluster.KMeans(init="k-means++", n_clusters=k, n_init="auto", random_state=0).fit(points).labels_``
     (``segmentation/segmenter.py:41-43``) with the Lloyd iterations on the device (``cn_kmeans_step``, float64 as sklearn).

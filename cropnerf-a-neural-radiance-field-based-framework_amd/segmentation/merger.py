@@ -85,13 +85,55 @@ def process_super_cluster(wo_occ, visible, label_frames, binary_thresh: int = 10
     return prop
 
 
-def load_projection_tree(super_cluster_dir, n_sub_clusters: int, visible_img_prefix: str = "visible_cluster",
-                         wo_occ_img_prefix: str = "wo_occ_cluster"):
-    """The PNG tree ``get_outputs_for_projections`` writes (``fruit_nerf.py:268-316``) and the reference's merger reads:
-    ``<dir>/cam_<j>/{wo_occ,visible}_cluster_<c>.png`` + ``<dir>/cam_<j>/label_frame*.png`` -> (wo_occ, visible
-    [n_cams, k, H, W] uint8, label_frames [n_cams, H, W] uint8), cameras ordered by their number."""
+LABEL_BATCH_FRAMES = 32  # masks per ops.instance_labels call (rule 3 of load_projection_tree)
+
+
+def find_label_frame(cam_dir, label_dir=None, mask_dir=None):
+    """Where one ``cam_<j>`` directory gets its label frame from, in this order: ``("cam", path)`` -- a
+    ``label_frame*.png`` that is already there; ``("label", path)`` -- ``label_dir/label_<name>`` or
+    ``label_dir/label_<stem>.png`` for the ``frame*.png`` the projection stage copied into the directory;
+    ``("mask", path)`` -- the colour instance mask ``mask_dir/<name>`` (or the same stem as .png / .jpg / .jpeg);
+    ``(None, None)``."""
     import glob
     import os
+
+    frames = glob.glob(os.path.join(str(cam_dir), "label_frame*.png"))
+    if frames:
+        return "cam", frames[0]
+    frames = sorted(glob.glob(os.path.join(str(cam_dir), "frame*.png")))
+    if not frames:
+        return None, None
+    name = os.path.basename(frames[0])
+    stem = os.path.splitext(name)[0]
+    if label_dir is not None:
+        for cand in (f"label_{name}", f"label_{stem}.png"):
+            if os.path.isfile(os.path.join(str(label_dir), cand)):
+                return "label", os.path.join(str(label_dir), cand)
+    if mask_dir is not None:
+        for cand in (name, stem + ".png", stem + ".jpg", stem + ".jpeg"):
+            if os.path.isfile(os.path.join(str(mask_dir), cand)):
+                return "mask", os.path.join(str(mask_dir), cand)
+    return None, None
+
+
+def load_projection_tree(super_cluster_dir, n_sub_clusters: int, visible_img_prefix: str = "visible_cluster",
+                         wo_occ_img_prefix: str = "wo_occ_cluster", *, label_dir=None, mask_dir=None, device="cuda",
+                         convert=None):
+    """The PNG tree ``get_outputs_for_projections`` writes (``fruit_nerf.py:268-316``) and the reference's merger reads:
+    ``<dir>/cam_<j>/{wo_occ,visible}_cluster_<c>.png`` + ``<dir>/cam_<j>/label_frame*.png`` -> (wo_occ, visible
+    [n_cams, k, H, W] uint8, label_frames [n_cams, H, W] uint8), cameras ordered by their number.
+
+    A camera without ``label_frame*.png`` gets its label frame as ``find_label_frame`` says: from ``label_dir`` (the
+    reference's ``SegmentationLabel``; the file is copied into the cam directory as ``overly_mask_with_projection`` does,
+    ``merger.py:170-171`` with scale 1), else from the colour masks of ``mask_dir`` (``SegmentationObject``), converted in
+    batches by ``convert`` (default ``ops.instance_labels`` on ``device``) and written as ``cam_<j>/label_<stem>.png``, so
+    that a second run finds them there.  Cameras that still have none get zeros, and ONE line on stderr says how many:
+    their sub-clusters carry no instance label and cannot be merged.  A label frame of another size than the projections
+    raises ``ValueError``."""
+    import glob
+    import os
+    import shutil
+    import sys
 
     from PIL import Image
 
@@ -102,12 +144,50 @@ def load_projection_tree(super_cluster_dir, n_sub_clusters: int, visible_img_pre
     def gray(path):
         return np.asarray(Image.open(path).convert("RGB"))[..., 0]
 
+    def checked(label, path, size):
+        if label.shape != size:
+            raise ValueError(f"{path}: label frame of {label.shape[1]} x {label.shape[0]}, projections of {size[1]} x {size[0]} "
+                             f"in {super_cluster_dir}")
+        return label
+
     wo, vis, lab = [], [], []
-    for _, d in cams:
+    masks, missing = [], 0  # rule 3: (camera position, cam directory, mask path)
+    for at, (_, d) in enumerate(cams):
         wo.append(np.stack([gray(os.path.join(d, f"{wo_occ_img_prefix}_{c}.png")) for c in range(n_sub_clusters)]))
         vis.append(np.stack([gray(os.path.join(d, f"{visible_img_prefix}_{c}.png")) for c in range(n_sub_clusters)]))
-        frames = glob.glob(os.path.join(d, "label_frame*.png"))
-        lab.append(np.asarray(Image.open(frames[0]).convert("L")) if frames else np.zeros(wo[-1].shape[1:], np.uint8))
+        size = wo[-1].shape[1:]
+        kind, path = find_label_frame(d, label_dir, mask_dir)
+        if kind == "cam":
+            lab.append(np.asarray(Image.open(path).convert("L")))
+            continue
+        if kind == "label":
+            lab.append(checked(np.asarray(Image.open(path).convert("L")), path, size))
+            shutil.copyfile(path, os.path.join(d, os.path.basename(path)))
+            continue
+        lab.append(np.zeros(size, np.uint8))
+        if kind == "mask":
+            masks.append((at, d, path))
+        else:
+            missing += 1
+    if masks:
+        from ..fruit_nerf.utils.convert_segmentation_img_to_label import device_convert, read_rgb
+
+        convert = convert or device_convert(device)
+        for b in range(0, len(masks), LABEL_BATCH_FRAMES):
+            batch = masks[b:b + LABEL_BATCH_FRAMES]
+            rgb = [read_rgb(path) for _, _, path in batch]
+            for a, (at, _, path) in zip(rgb, batch):
+                checked(a[..., 0], path, wo[at].shape[1:])
+            try:
+                labels = np.asarray(convert(np.stack(rgb)))
+            except ValueError as e:  # more than 255 colours in a frame: say which files the batch indices mean
+                raise ValueError(f"{e} -- the batch is {[path for _, _, path in batch]}") from e
+            for label, (at, d, path) in zip(labels, batch):
+                lab[at] = np.ascontiguousarray(label, dtype=np.uint8)
+                Image.fromarray(lab[at]).save(os.path.join(d, f"label_{os.path.splitext(os.path.basename(path))[0]}.png"))
+    if missing:
+        print(f"{super_cluster_dir}: {missing} of {len(cams)} cameras have no label frame; their sub-clusters carry no "
+              f"instance label and cannot be merged", file=sys.stderr)
     return np.stack(wo), np.stack(vis), np.stack(lab)
 
 
@@ -183,16 +263,18 @@ def count_fruit(cluster_props: Sequence[Dict[int, Dict[str, np.ndarray]]], graph
 def count_from_projection_dir(projection_dir, n_super_clusters: int, n_sub_clusters: int, graph_partition: str = "clique",
                               binary_threshold: int = 100, frame_sampling_interval: int = 10, area_normalize: bool = False,
                               visible_img_prefix: str = "visible_cluster", wo_occ_img_prefix: str = "wo_occ_cluster",
-                              device="cuda"):
+                              device="cuda", label_dir=None, mask_dir=None):
     """``main`` (``:359-437``) without the viewers: for every ``super_cluster_<i>`` directory of the projection tree, image
-    stage -> affinity -> partition; returns (total count, per-super-cluster counts, labels shifted to be unique, affinities)."""
+    stage -> affinity -> partition; returns (total count, per-super-cluster counts, labels shifted to be unique, affinities).
+    ``label_dir`` / ``mask_dir``: where cameras without a label frame find one (``load_projection_tree``)."""
     import os
     import random
 
     total, counts, labels_all, affinities = 0, [], [], []
     for i in range(n_super_clusters):
         wo, vis, lab = load_projection_tree(os.path.join(str(projection_dir), f"super_cluster_{i}"), n_sub_clusters,
-                                            visible_img_prefix, wo_occ_img_prefix)
+                                            visible_img_prefix, wo_occ_img_prefix, label_dir=label_dir, mask_dir=mask_dir,
+                                            device=device)
         prop = process_super_cluster(wo, vis, lab, binary_threshold, frame_sampling_interval, area_normalize, device)
         aff = calc_affinity(prop)
         random.seed(35)  # merger.py:23 graph_seed (the community partition draws from `random`)
@@ -234,9 +316,13 @@ def main(argv=None) -> int:
     n_sc, k = (min(17, len(pcd)) if a.super_cluster_idx == -1 else 1), pcd[0]["aabb"].shape[0]  # :398-399,421
     if a.super_cluster_idx != -1:
         raise SystemExit("a single --super_cluster_idx: rename that directory to super_cluster_0 or use the Python API")
+    # the reference's label_dir and its source (:382-383); a camera of the tree without a label frame looks there
+    data = os.path.join(a.base_dir, "training_data", a.recording_name)
+    label_dir, mask_dir = (d if os.path.isdir(d) else None
+                           for d in (os.path.join(data, "SegmentationLabel"), os.path.join(data, "SegmentationObject")))
     total, counts, labels_all, _ = count_from_projection_dir(projection_dir, n_sc, k, a.graph_partition, a.binary_threshold,
                                                              a.frame_sampling_interval, a.area_normalize, a.visible_img_prefix,
-                                                             a.wo_occ_img_prefix)
+                                                             a.wo_occ_img_prefix, label_dir=label_dir, mask_dir=mask_dir)
     for i, n in enumerate(counts):
         print(f"{i}_th super cluster has: {n}.")
     print(f"Total bool: {total}")  # sic (:437)

@@ -867,6 +867,25 @@ int cn_contour_largest(const uint8_t* gray, const int32_t* roi, int32_t num_imag
                        int32_t* start, int32_t* vertex_count, int32_t* label, int32_t* label_count, void* workspace,
                        size_t workspace_bytes, cn_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Colour instance masks -> the label frames the stage above reads (fruit_nerf/utils/convert_segmentation_img_to_label.py).
+ * frames [F,H,W,3] uint8 RGB.  A pixel's key is B << 16 | G << 8 | R.  A black pixel (key 0) gets label 0; any other pixel
+ * gets 1 + the number of distinct non-zero keys of the SAME frame that are smaller than its own.  colors[f][l] is the key
+ * that received label l in frame f (0 for l = 0 and for l > n), num_colors[f] = n, the count of distinct non-black colours.
+ * That is the row index in numpy.unique(bgr.reshape(-1, 3), axis=0) of the frame as cv2.imread holds it whenever the frame
+ * has a black pixel.  The reference numbers the colours 1..n in the iteration order of a Python set, an arbitrary
+ * bijection; every consumer compares labels for equality within one frame and against 0 only, so the fruit count and the
+ * partition do not depend on which bijection is taken, and this one is deterministic.
+ * Departures: a frame without a black pixel is valid (labels start at 1; the reference raises KeyError); a frame with more
+ * than 255 non-black colours is REPORTED, not wrapped into a uint8: num_colors[f] = 256, that frame's labels and colors are
+ * unspecified, the other frames of the batch are unaffected.
+ * num_frames == 0 or height * width == 0: nothing to do, CN_OK.  The workspace holds the per-frame key tables; they are
+ * cleared on `stream` at every call. */
+size_t cn_instance_labels_workspace_bytes(int32_t num_frames);
+int cn_instance_labels(const uint8_t* frames /* [F,H,W,3], RGB */, int32_t num_frames, int32_t height, int32_t width,
+                       uint8_t* labels /* [F,H,W] */, uint32_t* colors /* [F,256] */, int32_t* num_colors /* [F] */,
+                       void* workspace, size_t workspace_bytes, cn_stream_t stream);
+
 /* K-means sub-clustering of one super-cluster (segmentation/segmenter.py:28-45: sklearn KMeans(init="k-means++",
  * n_clusters=k, n_init="auto", random_state=0), called per super-cluster at :153-181).  ONE Lloyd iteration in float64, as
  * sklearn's _kmeans_single_lloyd: labels[i] <- index of the nearest of the k centres [k,3] (first minimum); *changed |= 1
