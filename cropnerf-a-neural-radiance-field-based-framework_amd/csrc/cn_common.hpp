@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cassert>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -114,6 +115,10 @@ inline GridDev make_grid_dev(const cn_grid& g) {
   d.half = g.table_dtype == CN_TABLE_F16;
   d.pos_offset = g.layout == CN_GRID_TCNN ? 0.5f : 0.f;
   const unsigned T = 1u << g.log2_table_size;
+  // INVARIANT: on every level m1 and m2 have the same parity -- both hash primes (odd) or both powers of two >= 2 (even).  The
+  // x-pair gathers rely on it: bit 0 of the index x ^ iy m1 ^ iz m2 is then the same for the (y, z) rows ff and cc, the same
+  // for cf and fc, and the two differ exactly when m1 is odd (hash_level_xpair_issue, hash_level_pk_issue).
+  static_assert(((CN_P1 ^ CN_P2) & 1u) == 0u, "the hash primes share their parity");
   for (int i = 0; i < CN_MAX_LEVELS; ++i) {
     const bool live = i < g.num_levels;
     d.scale[i] = live ? g.scalings[i] : 0.f;
@@ -122,6 +127,7 @@ inline GridDev make_grid_dev(const cn_grid& g) {
     d.m1[i] = b ? 1u << b : CN_P1;
     d.m2[i] = b ? 1u << (2 * b) : CN_P2;
     d.mask[i] = b ? (1u << (3 * b)) - 1u : T - 1u;
+    assert(((d.m1[i] ^ d.m2[i]) & 1u) == 0u);  // the invariant above
   }
   return d;
 }
@@ -274,17 +280,31 @@ struct Cell {
 };
 // OFFSET = false: pos_offset is known to be 0 (torch layout in the kernels specialised for it): plain products, which
 // hipcc contracts with the subtraction below exactly as the round-1 kernels did.
-template <bool OFFSET = true>
+// NONNEG = true: the caller guarantees sx, sy, sz >= 0 -- positions from normalize_position (in (0, 1), or 0), a positive scale
+// and pos_offset >= 0.  Then the conversion to int (round toward zero) IS the floor, and v_fract_f32 (x - floor(x), exact for
+// x >= 0: the difference of two floats of one binade or the next lower ones) IS the offset: two instructions per axis
+// instead of three, same values.  Only with OFFSET, where the scaled coordinate is one explicit fmaf: without it hipcc
+// contracts px * scale - floor(.) into one fma, which the fraction of the ROUNDED product does not reproduce.
+template <bool OFFSET = true, bool NONNEG = false>
 __device__ __forceinline__ Cell hash_cell(const Lvl& lv, float pos_offset, float px, float py, float pz) {
+  static_assert(OFFSET || !NONNEG, "the floor-free form needs the explicit fmaf of OFFSET");
   const float sx = OFFSET ? fmaf(px, lv.scale, pos_offset) : px * lv.scale;
   const float sy = OFFSET ? fmaf(py, lv.scale, pos_offset) : py * lv.scale;
   const float sz = OFFSET ? fmaf(pz, lv.scale, pos_offset) : pz * lv.scale;
-  const float fx = floorf(sx), fy = floorf(sy), fz = floorf(sz);
   Cell c;
-  c.ox = sx - fx;
-  c.oy = sy - fy;
-  c.oz = sz - fz;
-  const unsigned ix = (unsigned)(int)fx, iy = (unsigned)(int)fy, iz = (unsigned)(int)fz;
+  unsigned ix, iy, iz;
+  if constexpr (NONNEG) {
+    c.ox = __builtin_amdgcn_fractf(sx);
+    c.oy = __builtin_amdgcn_fractf(sy);
+    c.oz = __builtin_amdgcn_fractf(sz);
+    ix = (unsigned)(int)sx, iy = (unsigned)(int)sy, iz = (unsigned)(int)sz;
+  } else {
+    const float fx = floorf(sx), fy = floorf(sy), fz = floorf(sz);
+    c.ox = sx - fx;
+    c.oy = sy - fy;
+    c.oz = sz - fz;
+    ix = (unsigned)(int)fx, iy = (unsigned)(int)fy, iz = (unsigned)(int)fz;
+  }
   c.hx0 = ix;
   c.hx1 = ix + 1u;
   // 24-bit multiplies (v_mul_u32_u24, full rate; a 32-bit v_mul_lo_u32 is a quarter-rate instruction): cell indices are far
@@ -390,26 +410,29 @@ struct XpLoads {
   typedef _Float16 h2 __attribute__((ext_vector_type(2)));
   typename std::conditional<HALF, h4, f4>::type pr[4];   // aligned pairs, rows (y, z) = ff, cf, fc, cc
   typename std::conditional<HALF, h2, float2>::type up[4];  // upper-x corners of lanes with an odd x index
-  unsigned bits;  // bit r: the lower corner is the SECOND entry of pair r; bit 4: odd x index
+  // bit 0: the lower corner is the SECOND entry of pair 0 (row ff); bit 4: odd x index.  ONE parity bit per cell: m1 and m2
+  // share their parity (make_grid_dev), so row cc has the parity of row ff, and rows cf and fc have it flipped when m1 is odd
+  unsigned bits;
+  unsigned flip;  // m1 & 1: a compile-time 1 where the level record is (lane_level_rec<false>)
   float ox, oy, oz;
 };
 template <bool HALF = false>
 __device__ __forceinline__ XpLoads<HALF> hash_level_xpair_issue(const void* __restrict__ table, const Lvl& lv, float pos_offset,
                                                                 float px, float py, float pz) {
-  const Cell k = hash_cell(lv, pos_offset, px, py, pz);
+  const Cell k = hash_cell<true, true>(lv, pos_offset, px, py, pz);  // positions come from normalize_position: see hash_cell
   const char* base = reinterpret_cast<const char*>(table);
   const unsigned pair_mask = lv.mask & ~1u;
   const unsigned hyz[4] = {k.hy0 ^ k.hz0, k.hy1 ^ k.hz0, k.hy0 ^ k.hz1, k.hy1 ^ k.hz1};
   const bool odd = (k.hx0 & 1u) != 0u;
   XpLoads<HALF> L;
-  L.bits = odd ? 16u : 0u;
+  L.bits = (odd ? 16u : 0u) | ((k.hx0 ^ hyz[0]) & 1u);
+  L.flip = lv.m1 & 1u;
   L.ox = k.ox;
   L.oy = k.oy;
   L.oz = k.oz;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const unsigned x = k.hx0 ^ hyz[r];
-    L.bits |= (x & 1u) << r;
     const unsigned e = (x & pair_mask) + lv.off;  // first entry of the aligned pair (level offsets are even)
     if constexpr (HALF) L.pr[r] = *reinterpret_cast<const typename XpLoads<HALF>::h4*>(base + (size_t)(e << 2));
     else L.pr[r] = *reinterpret_cast<const typename XpLoads<HALF>::f4*>(base + (size_t)(e << 3));
@@ -432,7 +455,8 @@ __device__ __forceinline__ XpLoads<HALF> hash_level_xpair_issue(const void* __re
 // Which entry of an aligned pair is the lower-x corner depends on the row's hash parity; instead of SELECTING the values (six
 // conditional moves per row: lo / hi of two features, and the separately loaded upper corner of odd cells) the x WEIGHTS are
 // selected -- row value = a wa + b wb + u ox with (wa, wb) = (mx, ox') or (ox', mx), ox' = 0 for odd cells (their upper corner
-// is u; u is zero for even cells): two conditional moves per row and one more packed multiply-add.
+// is u; u is zero for even cells): one more packed multiply-add per row, and two conditional moves per CELL -- the four rows'
+// parities follow from one bit.
 template <bool HALF = false>
 __device__ __forceinline__ float2 hash_level_xpair_blend(const XpLoads<HALF>& L) {
   const bool odd = (L.bits & 16u) != 0u;
@@ -440,11 +464,14 @@ __device__ __forceinline__ float2 hash_level_xpair_blend(const XpLoads<HALF>& L)
   const float ox = L.ox, oy = L.oy, oz = L.oz;
   const float mx = 1.f - ox, my = 1.f - oy, mz = 1.f - oz;
   const float oxe = odd ? 0.f : ox;
+  // rows ff and cc take (wa0, wb0); rows cf and fc the same pair, swapped when m1 is odd (one parity bit per cell, XpLoads)
+  const bool second0 = (L.bits & 1u) != 0u, flip = L.flip != 0u;
+  const float wa0 = second0 ? oxe : mx, wb0 = second0 ? mx : oxe;
+  const float wa1 = flip ? wb0 : wa0, wb1 = flip ? wa0 : wb0;
   v2f row[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const bool second = ((L.bits >> r) & 1u) != 0u;
-    const float wa = second ? oxe : mx, wb = second ? mx : oxe;
+    const float wa = (r == 1 || r == 2) ? wa1 : wa0, wb = (r == 1 || r == 2) ? wb1 : wb0;
     v2f a, b, u;
     a.x = (float)L.pr[r].x;
     a.y = (float)L.pr[r].y;
@@ -452,7 +479,11 @@ __device__ __forceinline__ float2 hash_level_xpair_blend(const XpLoads<HALF>& L)
     b.y = (float)L.pr[r].w;
     u.x = (float)L.up[r].x;
     u.y = (float)L.up[r].y;
+    // each row is blended between two pins, in load order: with the weights shared between the rows hipcc otherwise waits for
+    // the last load before it blends the first row, instead of blending row by row as the loads return (vmcnt 3, 2, 1, 0)
+    asm volatile("" : "+v"(a), "+v"(b), "+v"(u));
     row[r] = u * ox + (b * wb + a * wa);
+    asm volatile("" : "+v"(row[r]));
   }
   const v2f a2 = row[3] * oy + row[2] * my, b2 = row[1] * oy + row[0] * my;
   const v2f rv = a2 * oz + b2 * mz;
@@ -571,13 +602,15 @@ typedef unsigned u32x2p __attribute__((ext_vector_type(2)));
 struct PkLoads {
   u32x2p pr[4];    // the aligned pair holding the lower-x corner of rows (y, z) = ff, cf, fc, cc
   unsigned up[4];  // the upper-x corner of each row, loaded separately when the x index is odd
-  unsigned bits;   // bit r: the lower-x corner is the pair's second entry; bit 4: odd x index
+  unsigned bits;   // bit 0: the lower-x corner of row ff is the pair's second entry; bit 4: odd x index
+  unsigned flip;   // m1 & 1: rows cf and fc have row ff's parity flipped, row cc has it as it is (see XpLoads)
   unsigned wxy, wzz;  // interpolation weights as packed fp16 pairs (x, y) and (z, z)
 };
 template <bool OFFSET = true>
 __device__ __forceinline__ PkLoads hash_level_pk_issue(const void* __restrict__ table, const Lvl& lv, float pos_offset, float px,
                                                        float py, float pz) {
-  const Cell k = hash_cell<OFFSET>(lv, pos_offset, px, py, pz);
+  // positions come from normalize_position: the floor-free cell where the scaled coordinate is an explicit fmaf (hash_cell)
+  const Cell k = hash_cell<OFFSET, OFFSET>(lv, pos_offset, px, py, pz);
   const char* base = reinterpret_cast<const char*>(table);
   const unsigned pair_mask = lv.mask & ~1u;
   const unsigned hyz[4] = {k.hy0 ^ k.hz0, k.hy1 ^ k.hz0, k.hy0 ^ k.hz1, k.hy1 ^ k.hz1};
@@ -589,11 +622,11 @@ __device__ __forceinline__ PkLoads hash_level_pk_issue(const void* __restrict__ 
     L.wzz = __builtin_bit_cast(unsigned, zz);
   }
   const bool odd = (k.hx0 & 1u) != 0u;
-  L.bits = odd ? 16u : 0u;
+  L.bits = (odd ? 16u : 0u) | ((k.hx0 ^ hyz[0]) & 1u);
+  L.flip = lv.m1 & 1u;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {  // level offsets are even, so the aligned pair of entry e is e & ~1
     const unsigned x = k.hx0 ^ hyz[r];
-    L.bits |= (x & 1u) << r;
     L.pr[r] = *reinterpret_cast<const u32x2p*>(base + (size_t)(((x & pair_mask) + lv.off) << 2));
     L.up[r] = 0u;
   }
@@ -610,9 +643,10 @@ __device__ __forceinline__ PkLoads hash_level_pk_issue(const void* __restrict__ 
 __device__ __forceinline__ unsigned hash_level_pk_blend(const PkLoads& L) {
   const bool odd = (L.bits & 16u) != 0u;
   f16x2 lo[4], hi[4];  // lower-x / upper-x corner of each row
+  const bool second0 = (L.bits & 1u) != 0u, second1 = ((L.bits ^ L.flip) & 1u) != 0u;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const bool second = (L.bits & (1u << r)) != 0u;
+    const bool second = (r == 1 || r == 2) ? second1 : second0;
     const unsigned a = L.pr[r].x, b = L.pr[r].y;
     lo[r] = __builtin_bit_cast(f16x2, second ? b : a);
     const unsigned upv = L.up[r];  // (a value: the conditional below on the array element itself selects an address)
@@ -645,11 +679,14 @@ __device__ __forceinline__ unsigned hash_level_pk(const void* __restrict__ table
 // copy the element into a scalar first.
 
 // torch.linspace(0,1,steps)[i] (CPU kernel: symmetric around the midpoint)
-__device__ __forceinline__ float linspace01(int i, int steps) {
-  float step = 1.f / (float)(steps - 1);
+// step = linspace_step(steps), computed once on the host: the same correctly rounded quotient as the device's division,
+// which costs a dozen VALU instructions wherever it stands in vector code
+inline float linspace_step(int steps) { return 1.f / (float)(steps - 1); }
+__device__ __forceinline__ float linspace01(int i, int steps, float step) {
   int half = steps / 2;
   return i < half ? step * (float)i : 1.f - step * (float)(steps - i - 1);
 }
+__device__ __forceinline__ float linspace01(int i, int steps) { return linspace01(i, steps, 1.f / (float)(steps - 1)); }
 
 __device__ __forceinline__ float spacing_fn(int mode, float x) {
   if (mode == CN_SPACING_PIECEWISE) return x < 1.f ? x / 2.f : 1.f - 1.f / (2.f * x);

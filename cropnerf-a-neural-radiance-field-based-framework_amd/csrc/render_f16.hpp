@@ -86,7 +86,7 @@ __global__ void __launch_bounds__(FUSED_THREADS, CN_F16_WAVES_PER_SIMD) render_f
     const float* bins = A.bins ? A.bins + r * (long long)(S + 1) : nullptr;
     auto edge = [&](int i) -> float {
       i = min(i, S);
-      return bins ? bins[i] : spacing_to_euclid(A.spacing, linspace01(i, S + 1), sn, sf);
+      return bins ? bins[i] : spacing_to_euclid(A.spacing, linspace01(i, S + 1, A.lin_step), sn, sf);
     };
 
     CompositeState st;

@@ -261,6 +261,7 @@ struct FusedArgs {
   const float* bins;  // [R,S+1] or null
   long long num_rays;
   int S;
+  float lin_step;  // linspace_step(S + 1) = 1 / S: the uniform sampler's step, divided once on the host
   int spacing;
   int bg_mode;
   float bg[3];
@@ -390,7 +391,7 @@ __global__ void __launch_bounds__(FUSED_THREADS, CN_FUSED_MIN_WAVES_PER_SIMD) re
     const float* bins = A.bins ? A.bins + r * (long long)(S + 1) : nullptr;
     auto edge = [&](int i) -> float {
       i = min(i, S);
-      return bins ? bins[i] : spacing_to_euclid(A.spacing, linspace01(i, S + 1), sn, sf);
+      return bins ? bins[i] : spacing_to_euclid(A.spacing, linspace01(i, S + 1, A.lin_step), sn, sf);
     };
 
     // ---- per-ray colour bias: bc0 + Wc0[:, sh].SH(d) + Wc0[:, app].app  (lane n = neuron n) ------------------
@@ -869,6 +870,7 @@ static int launch_fused(const cn_field_params* params, const cn_scene* scene, co
   A.bins = bins;
   A.num_rays = num_rays;
   A.S = opts->num_samples;
+  A.lin_step = linspace_step(opts->num_samples + 1);
   A.spacing = opts->spacing;
   A.bg_mode = opts->bg_mode;
   A.bg[0] = opts->bg_color[0];

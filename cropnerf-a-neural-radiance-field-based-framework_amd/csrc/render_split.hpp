@@ -43,6 +43,11 @@ namespace cn {
 // -DCN_ABLATE_GATHER_LEVELS=4 / 8 (the coarsest 4 / 8 levels read no table entry and hash nothing): 2.573 / 2.490 ms against
 // 2.597 -- the bound on what a cheaper (e.g. cell-major, one 64-byte line per cell) copy of the coarse levels could give
 // against 2.56 ms for the real thing.
+// VALU instructions per half-step of the split-bf16 team form (the headline; static counts of the compiled kernel, DESIGN.md
+// section 5): a gather wave's level evaluation is 74-78 instructions and 8 loads (one parity bit per cell selects the x weights
+// of all four rows, the cell index and offset are v_cvt_i32 / v_fract, no floor: cn_common.hpp), the uniform sampler's step is a
+// kernel argument (FusedArgs::lin_step: no division in vector code), and a matrix wave splits its 44 values per lane and
+// 16-sample tile into bf16 hi + lo pair by pair, 2.5 instructions per value (split_bf16_pair).
 // rays per team of the team gather (fp16 mode, half table): 2 = two neighbouring pixels of a row in a lane pair; 4 = a 2 x 2
 // pixel block in a lane quad, each gather wave taking 8 of the half-step's 32 samples for all four (default).  Measured at C2
 // (ms per batch, mean over the ten batches): 2 rays 1.60, 4 consecutive pixels of a row 1.48, 2 x 2 block 1.39; the 2 x 2
@@ -81,15 +86,29 @@ constexpr size_t SPLIT_LDS_BYTES_PACK = SPLIT_LDS_BYTES + (size_t)(SPLIT_PAIRS *
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-// fp32 values -> bf16 hi + bf16 lo (x ~ hi + lo to ~16 mantissa bits): the B operands of the split-bf16 matrix path
+// fp32 values -> bf16 hi + bf16 lo (x ~ hi + lo to ~16 mantissa bits): the B operands of the split-bf16 matrix path.
+// hi = bf16(x), lo = bf16(x - hi), both rounded to nearest even.  Written per PAIR of values -- one v_cvt_pk_bf16_f32 for two
+// hi parts, a shift and a mask to widen them again, one packed subtraction, one v_cvt_pk_bf16_f32 for two lo parts: 2.5
+// instructions per value.  (Written per value, hipcc splits the first two elements of every f32x4 one by one -- a convert with
+// a zero partner, a shift and a subtraction each, and a third convert to pack the pair: 3.5 per value.)
+typedef float f32x2s __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2s __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void split_bf16_pair(float x0, float x1, unsigned& hi, unsigned& lo) {
+  const f32x2s x = {x0, x1};
+  const unsigned h = __builtin_bit_cast(unsigned, __builtin_convertvector(x, bf16x2s));
+  const f32x2s hf = {__builtin_bit_cast(float, h << 16), __builtin_bit_cast(float, h & 0xffff0000u)};
+  hi = h;
+  lo = __builtin_bit_cast(unsigned, __builtin_convertvector(x - hf, bf16x2s));
+}
 __device__ __forceinline__ void split_bf16(const f32x4& a, const f32x4& b, bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float x = j < 4 ? a[j] : b[j - 4];
-    const __bf16 h = (__bf16)x;
-    hi[j] = h;
-    lo[j] = (__bf16)(x - (float)h);
-  }
+  unsigned h[4], l[4];
+  split_bf16_pair(a.x, a.y, h[0], l[0]);
+  split_bf16_pair(a.z, a.w, h[1], l[1]);
+  split_bf16_pair(b.x, b.y, h[2], l[2]);
+  split_bf16_pair(b.z, b.w, h[3], l[3]);
+  hi = __builtin_bit_cast(bf16x8, u32x4s{h[0], h[1], h[2], h[3]});
+  lo = __builtin_bit_cast(bf16x8, u32x4s{l[0], l[1], l[2], l[3]});
 }
 // acc += A . B with A = ah + al, B = bh + bl, dropping al . bl (v_mfma_f32_16x16x32_bf16, fp32 accumulation)
 __device__ __forceinline__ f32x4 mfma_split(const bf16x8& ah, const bf16x8& al, const bf16x8& bh, const bf16x8& bl, f32x4 acc) {
@@ -102,14 +121,10 @@ __device__ __forceinline__ f32x4 mfma_split(const bf16x8& ah, const bf16x8& al, 
 // A K block that holds only 16 real k values (the 16 base outputs feeding semantics layer 0 and colour layer 0) carries hi AND
 // lo of a lane's four values in one B operand: hi (as split_bf16 defines it) in elements 0-3, lo in elements 4-7 ...
 __device__ __forceinline__ bf16x8 split_bf16_k16(const f32x4& a) {
-  bf16x8 r;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const __bf16 h = (__bf16)a[j];
-    r[j] = h;
-    r[4 + j] = (__bf16)(a[j] - (float)h);
-  }
-  return r;
+  unsigned h[2], l[2];
+  split_bf16_pair(a.x, a.y, h[0], l[0]);
+  split_bf16_pair(a.z, a.w, h[1], l[1]);
+  return __builtin_bit_cast(bf16x8, u32x4s{h[0], h[1], l[0], l[1]});
 }
 // ... and the A images of those blocks repeat a lane's four weights in elements 4-7 (prep_kernel), so two products give all
 // four terms: acc += [ah | ah] . [bh | bl] + [al | al] . [bh | bl] = (ah + al) . (bh + bl)
@@ -242,7 +257,7 @@ __device__ __forceinline__ void split_ray_setup(const FusedArgs& A, long long q,
 
 __device__ __forceinline__ float split_edge(const FusedArgs& A, const SplitRay& ray, int i) {
   i = min(i, A.S);
-  return ray.bins ? ray.bins[i] : spacing_to_euclid(A.spacing, linspace01(i, A.S + 1), ray.sn, ray.sf);
+  return ray.bins ? ray.bins[i] : spacing_to_euclid(A.spacing, linspace01(i, A.S + 1, A.lin_step), ray.sn, ray.sf);
 }
 
 __device__ __forceinline__ void split_fill_edges(const FusedArgs& A, const SplitRay& ray, int c0, float* tb, int lane) {
@@ -421,7 +436,7 @@ __global__ void __launch_bounds__(SPLIT_THREADS) render_split_kernel(FusedArgs A
               const int chunk = PER_SAMPLE ? (int)rc.z : (k >> 1), half = k & 1;
               auto edge = [&](int i) -> float {
                 i = min(i, S);
-                return rbins ? rbins[i] : spacing_to_euclid(A.spacing, linspace01(i, S + 1), rsn, rsf);
+                return rbins ? rbins[i] : spacing_to_euclid(A.spacing, linspace01(i, S + 1, A.lin_step), rsn, rsf);
               };
               float px[2], py[2], pz[2];
               bool sel[2];
